@@ -3,8 +3,12 @@
 
 Headline (`value`): the regression training step -- DenseNet-BC forward (HIP kernels), spherical mover's Sinkhorn loss
 (HIP), backward (HIP), Adam -- at BASELINE configs[1] ("RegressionNetwork train.py, batch 64, 128 anchors, Sinkhorn
-blur .05", 240x320 crops).  The same JSON line carries the other legs of BASELINE's metric ("regression+projector;
-Sinkhorn ms/iter") as objects, each timed in this process on the launch stream:
+blur .05", 240x320 crops).  A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only that: it sets up, warms up,
+times the N steps and prints the line.  `--dump-outputs DIR` then writes what the last timed step computed (losses,
+predictions, a fixed sample of the gradients and updated weights) as DIR/<name>.npy; inputs and initial weights are seeded,
+so two builds can be compared output for output.
+With `--full` the same JSON line carries the other legs of BASELINE's metric ("regression+projector; Sinkhorn ms/iter")
+as objects, each timed in this process on the launch stream (`--legs` picks some of them, with or without `--full`):
   `projector`  GenProjector G step + D step at configs[2] (B=32/GPU, 128x256)        img/s, fraction of the f32-MFMA roof
   `joint`      regression -> rasteriser -> projector step at configs[3] (32/GPU)     img/s, fraction of the f32-MFMA roof
   `sinkhorn`   ms per eps-step at configs[1] and at configs[4]'s shape (B=16, N=256)  fraction of the 8 TB/s HBM roof
@@ -16,9 +20,9 @@ fixed -> weak scaling.  Launch either way:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
     python bench.py --gpus N          (no WORLD_SIZE in the environment: bench.py starts the N ranks itself)
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel family of the headline step, measured live with
-HIP events on the launch stream; `cpu_baseline` is the oracle (torch-CPU restatement, parity-pinned to the reference)
-timed on this box's host cores at a bounded batch.
+Prints ONE JSON line on rank 0.  `roofline` (with `families` among the legs) is for the dominant kernel family of the
+headline step, measured live with HIP events on the launch stream; `cpu_baseline` (`--full` only) is the oracle (torch-CPU
+restatement, parity-pinned to the reference) timed on this box's host cores at a bounded batch.
 """
 import argparse
 import json
@@ -790,6 +794,30 @@ def leg_joint(args, rank, world, dev, steps, warmup):
     return out
 
 
+DUMP_SAMPLE = 1 << 20   # elements kept of a larger output: a seeded sample, the same indices on every run of a geometry
+
+
+def dump_outputs(path, result, pred, model):
+    """`--dump-outputs`: what the last timed step computed -- its total loss and the five terms (what `step` returns), the
+    predictions (`last_pred`), and fixed seeded samples of the parameter gradients and of the weights Adam left -- as
+    <path>/<name>.npy, float32 (float64 stays float64).  About 8 MB at BASELINE's geometry."""
+    import numpy as np
+    loss, terms = result
+    arrays = {"loss": loss}
+    arrays.update(("loss_" + k, v) for k, v in terms.items())
+    arrays.update(("pred_" + k, v) for k, v in pred.items())
+    params = list(model.parameters())
+    arrays["grads_sample"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+    arrays["params_sample"] = torch.cat([p.detach().reshape(-1) for p in params])
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu() if t.dtype != torch.float64 else t.detach().cpu()
+        if name.endswith("_sample") and a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks (one process per GPU) ourselves and
     relay their output; the children see WORLD_SIZE and take the normal path."""
@@ -817,14 +845,23 @@ def main():
     ap.add_argument("--anchors", type=int, default=128)
     ap.add_argument("--crop_hw", type=int, nargs=2, default=(240, 320))
     ap.add_argument("--blur", type=float, default=.05)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--legs", default="all",
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline step: every leg below (or those --legs names), the collectives of a "
+                         "regression step and the CPU baseline")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--legs", default=None,
                     help="comma list of the extra objects on the line: projector,joint,sinkhorn,rasteriser,families "
-                         "(default all; 'none' = the headline regression step only)")
+                         "(default: none, all with --full; 'none' = the headline regression step only)")
     ap.add_argument("--workload", default="regression", choices=["regression", "projector", "joint"],
-                    help="regression = BASELINE's headline line with every leg as an object (default); projector / joint = "
+                    help="regression = BASELINE's headline line (default); projector / joint = "
                          "a line whose `value` is that leg alone (profiling runs)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (regression workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "regression":
+        ap.error("--dump-outputs writes the regression step's outputs: it needs --workload regression")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
 
@@ -836,6 +873,8 @@ def main():
                          % (args.gpus, world))
     dev = "cuda:%d" % local
     crop_hw = tuple(args.crop_hw)
+    if args.legs is None:
+        args.legs = "all" if args.full else "none"
     legs = {"projector", "joint", "sinkhorn", "rasteriser", "families"} if args.legs == "all" else \
         set(x for x in args.legs.split(",") if x and x != "none")
     par = "dp%d" % world if world > 1 else "single"
@@ -851,15 +890,24 @@ def main():
             dist.destroy_process_group()
         return
 
+    torch.manual_seed(0)   # the same initial weights on every run and rank (--dump-outputs compares builds output for output)
     tr = RegressionTrainer(anchors=args.anchors, crop_hw=crop_hw, blur=args.blur, device=dev, world=world)
     batch = synthetic_batch(args.batch, args.anchors, crop_hw, seed=1234 + rank, device=dev)
 
-    dt = run_timed(lambda: tr.step(batch), args.steps, args.warmup, world, dev)
+    last = [None]
+
+    def step():
+        last[0] = tr.step(batch)
+    dt = run_timed(step, args.steps, args.warmup, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], tr.last_pred, tr.model)
+    del last
 
     # live per-kernel timing: EVERY rank runs the instrumented steps (they contain DDP's all-reduce)
     fams = time_kernel_families(tr, batch, 2, args.batch, crop_hw) if "families" in legs else None
     peak_gb = round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)
-    reg_coll = collectives_of_a_step(lambda: tr.step(batch), [("encoder", tr.buckets or tr.ddp)])   # every rank steps; rank 0 reports
+    # every rank steps; rank 0 reports
+    reg_coll = collectives_of_a_step(lambda: tr.step(batch), [("encoder", tr.buckets or tr.ddp)]) if args.full else None
     del tr, batch
     _free_gpu()
     # the other legs of BASELINE's metric; every rank takes part (DDP collectives inside), rank 0 reports
@@ -949,7 +997,7 @@ def main():
             out["rasteriser"] = time_rasteriser(args.projector_batch, args.anchors, (128, 256), dev)
             out["rasteriser_n256"] = time_rasteriser(16, 256, (256, 512), dev)   # configs[4]'s per-GPU shape
         out.update(extra)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.anchors, crop_hw, args.blur)
         # the headline numbers of EVERY leg in one compact object: inside `roofline` (an object the driver's record keeps
         # whole) and once more as the LAST key of the line (what a truncated stdout tail still shows)

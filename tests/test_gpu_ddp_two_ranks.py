@@ -228,7 +228,7 @@ def test_bench_two_ranks_runs_every_leg_without_deadlock():
     env = dict(os.environ, EML_DIST_BACKEND="gloo", EML_SHARE_GPUS="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--projector_batch", "2", "--joint_batch", "2", "--no_cpu_baseline"],
+                        "--batch", "4", "--projector_batch", "2", "--joint_batch", "2", "--full", "--no_cpu_baseline"],
                        env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

@@ -21,7 +21,7 @@ echo "{\"collected_at_commit\": \"$COMMIT\", \"command\": \"rocprofv3 --kernel-t
 cp $OUT/${TAG}_pmc_summary.csv $OUT/${TAG}_pmc_summary.meta.json $REPO/profiles/
 head -40 $OUT/${TAG}_pmc_summary.csv
 if [ -z "$SKIP_BENCH" ]; then
-  timeout 900 python $REPO/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+  timeout 900 python $REPO/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 fi
 rm -rf /tmp/kst
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kst -o k -- python $REPO/bench.py --steps 3 --warmup 1 --no_cpu_baseline --legs families,sinkhorn,rasteriser > $OUT/${TAG}_kst.log 2>&1
