@@ -1,11 +1,12 @@
 """Mirror of the hot-path parts of the reference's ``RegressionNetwork/util.py``.
 
-``convert_to_panorama`` (reference ``util.py:222-245``) runs as one HIP kernel;
+``convert_to_panorama`` (reference ``util.py:222-245``) runs as one HIP kernel each way;
 ``sphere_points`` (``util.py:286-299``) and ``TonemapHDR`` (``util.py:36-66``) are the
 small host helpers the kept entry points need.  EXR/vtk/cv2 I/O is out of scope.
 """
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 
@@ -29,19 +30,47 @@ class _Rasterise(torch.autograd.Function):
         _lib.check(_lib.lib().eml_sg_rasterise_f32(_lib.ptr(dirs), _lib.ptr(sizes), _lib.ptr(colors),
                                                    _lib.ptr(out), B, N, H, W, _lib.current_stream()),
                    "eml_sg_rasterise_f32")
-        ctx.save_for_backward(dirs, sizes)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(dirs, sizes, colors)   # q = gout . colors enters d/d dirs and d/d sizes
+        else:
+            ctx.save_for_backward(dirs, sizes)
         ctx.hw = (H, W)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gout):
-        dirs, sizes = ctx.saved_tensors
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            raise NotImplementedError("convert_to_panorama: gradients wrt dirs/sizes are not on EMLight's "
-                                      "path (anchors and lobe widths are constants)")
+        need = ctx.needs_input_grad[:3]
         H, W = ctx.hw
-        B, N = sizes.shape
-        return None, None, rasterise_bwd_colors_raw(dirs, sizes, gout, (H, W)), None, None
+        if not (need[0] or need[1]):
+            dirs, sizes = ctx.saved_tensors
+            return None, None, rasterise_bwd_colors_raw(dirs, sizes, gout, (H, W)), None, None
+        dirs, sizes, colors = ctx.saved_tensors
+        gd, gs, gc = rasterise_bwd_raw(dirs, sizes, colors, gout, (H, W), need=need)
+        return gd, gs, gc, None, None
+
+
+def rasterise_bwd_raw(dirs, sizes, colors, gout, pano_hw, exhaustive=False, need=(True, True, True)):
+    """d loss / d (dirs (B, 3N), sizes (B, N), colors (B, 3N)) in one ``eml_sg_rasterise_bwd_f32`` launch (+ its tile-order
+    reduce): the colours-only kernel's light lists and tiles with four more sums per light.  ``need``: which of the three to
+    return (the others are ``None`` and not written); the colour gradient is bit for bit ``rasterise_bwd_colors_raw``'s.
+    ``exhaustive``: every light for every tile (what the culled launch equals bit for bit)."""
+    H, W = pano_hw
+    B, N = sizes.shape
+    if not any(need):
+        raise ValueError("rasterise_bwd_raw: no gradient requested")
+    L = _lib.lib()
+    gout = gout.contiguous()
+    dev = gout.device
+    gd = torch.empty(B, 3 * N, dtype=torch.float32, device=dev) if need[0] else None
+    gs = torch.empty(B, N, dtype=torch.float32, device=dev) if need[1] else None
+    gc = torch.empty(B, 3 * N, dtype=torch.float32, device=dev) if need[2] else None
+    work = torch.empty(max(1, L.eml_sg_rasterise_bwd_full_work_floats(B, N, int(H), int(W))), dtype=torch.float32, device=dev)
+    _lib.check(L.eml_sg_rasterise_bwd_f32(_lib.ptr(dirs), _lib.ptr(sizes), _lib.ptr(colors), _lib.ptr(gout), _lib.ptr(gd),
+                                          _lib.ptr(gs), _lib.ptr(gc), _lib.ptr(work), B, N, int(H), int(W), 1 if exhaustive else 0,
+                                          _lib.current_stream()),
+               "eml_sg_rasterise_bwd_f32")
+    return gd, gs, gc
 
 
 def rasterise_bwd_colors_raw(dirs, sizes, gout, pano_hw, exhaustive=False, legacy=False):
@@ -85,7 +114,9 @@ def convert_to_panorama(dirs, sizes, colors, pano_hw=(128, 256)):
     """SG lobes -> equirect panorama ``(B, 3, H, W)``; reference ``util.py:222-245``.
 
     dirs ``(B, 3N)``, sizes ``(B, N)``, colors ``(B, 3N)``.  ``pano_hw`` defaults to the
-    reference's hard-coded 128 x 256 (``W`` must be ``2H``).  Differentiable wrt ``colors``.
+    reference's hard-coded 128 x 256 (``W`` must be ``2H``).  Differentiable in all three inputs, like the reference's
+    torch arithmetic (once: the backward is not itself differentiable).  A backward that needs only ``colors`` runs the
+    colour-gradient kernel alone; one that needs ``dirs`` or ``sizes`` runs the full-gradient kernel.
     """
     H, W = pano_hw
     d = _lib.require_gpu_tensor(dirs, "dirs")

@@ -1,4 +1,4 @@
-// Spherical-Gaussian lobes -> equirectangular panorama, forward and d/d(colors).
+// Spherical-Gaussian lobes -> equirectangular panorama, forward, d/d(colors) and d/d(dirs, sizes, colors).
 //
 // Replaces the per-light Python loop of convert_to_panorama
 // (reference RegressionNetwork/util.py:222-245): there each of the N lights costs ~6 ATen
@@ -343,6 +343,167 @@ __global__ __launch_bounds__(256) void sg_reduce_tiles_kernel(const float* __res
   gcolors[e] = s;
 }
 
+// All three gradients (autograd of util.py:239-244 wrt dirs, sizes and colors).  With t = (d.p - 1)/s, e = exp(t) and
+// q(p) = sum_c gout_c(p) colors_c:  d/d colors_c = sum_p gout_c e,  d/d s = (1/s^2) sum_p q e (1 - d.p),  d/d d = (1/s) sum_p q e p.
+// The colours-only kernel above with the colours staged beside the lobes (the forward's 32-byte Lobe) and four more wave sums
+// per survivor: the size sum and the three direction sums, parked in the same wave-private LDS row next to the colour sums
+// (kSums floats per light), partials [B][tiles][N][kSums].  The colour sums are formed by exactly the colours-only kernel's
+// expressions, so with sg_reduce_full_kernel they are bit for bit what eml_sg_rasterise_bwd_colors_ex_f32 returns.  Every
+// per-pixel term is e times a finite factor: a culled light contributes exactly 0 to all seven sums, as in the colours-only
+// kernel.  LDS: 4 + 16 + 2 + 14 KiB.
+constexpr int kSums = 7;   // r, g, b, size, dx, dy, dz
+
+__global__ __launch_bounds__(256) void sg_rasterise_bwd_full_tiled_kernel(
+    const float* __restrict__ dirs, const float* __restrict__ sizes, const float* __restrict__ colors,
+    const float* __restrict__ gout, float* __restrict__ partial, int N, int H, int W, float step, int exhaustive) {
+  __shared__ Lobe lobes[kChunk];
+  __shared__ Lobe kept[4][kChunk];
+  __shared__ int keptidx[4][kChunk];
+  __shared__ float accw[4][kChunk][kSums];
+  __shared__ float sin_t[kTileH], cos_t[kTileH], sin_p[kTileW], cos_p[kTileW];
+  const int b = blockIdx.z;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  Lobe pre;
+  auto preload = [&](int base) {
+    const size_t li = (size_t)b * N + min(base + tid, N - 1);
+    pre.dx = dirs[3 * li + 0];
+    pre.dy = dirs[3 * li + 1];
+    pre.dz = dirs[3 * li + 2];
+    pre.k2 = sizes[li];          // divided when it is committed to LDS
+    pre.r = colors[3 * li + 0];
+    pre.g = colors[3 * li + 1];
+    pre.b = colors[3 * li + 2];
+    pre.pad = 0.f;
+  };
+  if (tid < kChunk) preload(0);
+  if (tid < kTileH) sincosf(((float)(blockIdx.y * kTileH + tid) + 0.5f) * step, &sin_t[tid], &cos_t[tid]);
+  else if (tid < kTileH + kTileW)
+    sincosf(((float)(blockIdx.x * kTileW + tid - kTileH) + 0.5f) * step, &sin_p[tid - kTileH], &cos_p[tid - kTileH]);
+  __syncthreads();
+  const int cw = (wave & 1) * 16 + (lane & 15), r0 = (wave >> 1) * 8 + (lane >> 4), r1 = r0 + 4;
+  const int w = blockIdx.x * kTileW + cw;
+  const int h0 = blockIdx.y * kTileH + r0, h1 = h0 + 4;
+  const float p0x = sin_t[r0] * cos_p[cw], p0y = sin_t[r0] * sin_p[cw], p0z = cos_t[r0];
+  const float p1x = sin_t[r1] * cos_p[cw], p1y = sin_t[r1] * sin_p[cw], p1z = cos_t[r1];
+  float cx, cy, cz, rr;   // bounding cap of the wave's patch: exactly the forward's
+  {
+    auto lane_of = [](float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); };
+    cx = lane_of(p0x, 56) + lane_of(p1x, 7);
+    cy = lane_of(p0y, 56) + lane_of(p1y, 7);
+    cz = lane_of(p0z, 56) + lane_of(p1z, 7);
+    const float inv = rsqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+    cx *= inv, cy *= inv, cz *= inv;
+    const float a0 = p0x - cx, a1 = p0y - cy, a2 = p0z - cz, b0 = p1x - cx, b1 = p1y - cy, b2 = p1z - cz;
+    const float d2 = fmaxf(fmaf(a2, a2, fmaf(a1, a1, a0 * a0)), fmaf(b2, b2, fmaf(b1, b1, b0 * b0)));
+    rr = sqrtf(eml::wave_max_dpp(d2)) * 1.0001f + 1e-6f;
+  }
+  // the lane's two pixels of the output gradient (0 off the map)
+  const size_t plane = (size_t)H * W;
+  const float* g = gout + (size_t)b * 3 * plane;
+  float g0[3] = {0.f, 0.f, 0.f}, g1[3] = {0.f, 0.f, 0.f};
+  if (w < W && h0 < H) {
+    const size_t o = (size_t)h0 * W + w;
+    g0[0] = g[o]; g0[1] = g[plane + o]; g0[2] = g[2 * plane + o];
+  }
+  if (w < W && h1 < H) {
+    const size_t o = (size_t)h1 * W + w;
+    g1[0] = g[o]; g1[1] = g[plane + o]; g1[2] = g[2 * plane + o];
+  }
+  const int tile = blockIdx.y * gridDim.x + blockIdx.x, ntiles = gridDim.x * gridDim.y;
+  float* out = partial + ((size_t)b * ntiles + tile) * N * kSums;
+  for (int base = 0; base < N; base += kChunk) {
+    const int cnt = min(kChunk, N - base);
+    if (base > 0) __syncthreads();   // the previous chunk's lobes / lists / sums are no longer read
+    if (tid < cnt) {
+      Lobe L = pre;
+      L.k2 = kLog2e / pre.k2;
+      lobes[tid] = L;
+    }
+    for (int i = lane; i < kChunk * kSums; i += 64) (&accw[wave][0][0])[i] = 0.f;
+    __syncthreads();
+    if (base + kChunk < N && tid < kChunk) preload(base + kChunk);
+    int n = 0;
+    for (int j = 0; j < cnt; j += 64) {
+      const int li = j + lane;
+      const Lobe L = lobes[min(li, cnt - 1)];
+      const float len = sqrtf(fmaf(L.dz, L.dz, fmaf(L.dy, L.dy, L.dx * L.dx)));
+      const float s_ = fmaf(L.dz, cz, fmaf(L.dy, cy, L.dx * cx)) + fmaf(len, rr, 1e-5f * (1.0f + len));
+      const bool odd = !(L.k2 > 0.f) || L.k2 > 3.0e38f || !(len < 3.0e38f);   // as in the forward: never cull these
+      const bool keep = li < cnt && (exhaustive || odd || !((s_ - 1.0f) * L.k2 <= kCull));
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+      const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      if (keep) {
+        kept[wave][pos] = L;
+        keptidx[wave][pos] = li;
+      }
+      n += __builtin_popcountll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int i = 0; i < n; ++i) {
+      const Lobe L = kept[wave][i];   // broadcast reads
+      const int li = keptidx[wave][i];
+      const float dot0 = fmaf(L.dz, p0z, fmaf(L.dy, p0y, L.dx * p0x));
+      const float dot1 = fmaf(L.dz, p1z, fmaf(L.dy, p1y, L.dx * p1x));
+      const float e0 = __builtin_amdgcn_exp2f((dot0 - 1.0f) * L.k2);
+      const float e1 = __builtin_amdgcn_exp2f((dot1 - 1.0f) * L.k2);
+      // the colours-only kernel's three sums, expression for expression
+      const float sr = eml::wave_sum_dpp(fmaf(g1[0], e1, g0[0] * e0));
+      const float sg = eml::wave_sum_dpp(fmaf(g1[1], e1, g0[1] * e0));
+      const float sb = eml::wave_sum_dpp(fmaf(g1[2], e1, g0[2] * e0));
+      const float q0 = fmaf(g0[2], L.b, fmaf(g0[1], L.g, g0[0] * L.r)) * e0;   // q e of the two pixels
+      const float q1 = fmaf(g1[2], L.b, fmaf(g1[1], L.g, g1[0] * L.r)) * e1;
+      const float ss = eml::wave_sum_dpp(fmaf(q1, 1.0f - dot1, q0 * (1.0f - dot0)));
+      const float sx = eml::wave_sum_dpp(fmaf(q1, p1x, q0 * p0x));
+      const float sy = eml::wave_sum_dpp(fmaf(q1, p1y, q0 * p0y));
+      const float sz = eml::wave_sum_dpp(fmaf(q1, p1z, q0 * p0z));
+      if (lane == 0) {
+        float* a = accw[wave][li];
+        a[0] = sr;
+        a[1] = sg;
+        a[2] = sb;
+        a[3] = ss;
+        a[4] = sx;
+        a[5] = sy;
+        a[6] = sz;
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < cnt * kSums; i += 256) {
+      const float* a0 = &accw[0][0][0];
+      out[(size_t)base * kSums + i] =
+          (a0[i] + a0[kChunk * kSums + i]) + (a0[2 * kChunk * kSums + i] + a0[3 * kChunk * kSums + i]);
+    }
+  }
+}
+
+// The per-tile partials added in tile order (the association of sg_reduce_tiles_kernel), then the chain rule's factors:
+// 1/s^2 for the size sum, 1/s for the direction sums.  A NULL output is not written.
+__global__ __launch_bounds__(256) void sg_reduce_full_kernel(const float* __restrict__ partial, const float* __restrict__ sizes,
+                                                             int ntiles, int N, float* __restrict__ gdirs,
+                                                             float* __restrict__ gsizes, float* __restrict__ gcolors,
+                                                             int total) {
+  const int e = blockIdx.x * 256 + threadIdx.x;   // (b, light, sum)
+  if (e >= total) return;
+  const int nk = N * kSums;
+  const int b = e / nk, r = e - b * nk, i = r / kSums, k = r - i * kSums;
+  float* dst = k < 3 ? gcolors : k == 3 ? gsizes : gdirs;
+  if (!dst) return;
+  const float* p = partial + (size_t)b * ntiles * nk + r;
+  float s = 0.f;
+  for (int t = 0; t < ntiles; ++t) s += p[(size_t)t * nk];
+  const size_t li = (size_t)b * N + i;
+  if (k < 3) {
+    gcolors[3 * li + k] = s;
+  } else {
+    const float sz = sizes[li];
+    if (k == 3) gsizes[li] = s / sz / sz;
+    else gdirs[3 * li + (k - 4)] = s / sz;
+  }
+}
+
 }  // namespace
 
 extern "C" int eml_sg_rasterise_ex_f32(const float* dirs, const float* sizes, const float* colors, float* out, int B,
@@ -420,4 +581,35 @@ extern "C" int eml_sg_rasterise_bwd_colors_ex_f32(const float* dirs, const float
   hipLaunchKernelGGL(sg_reduce_tiles_kernel, dim3((total + 255) / 256), dim3(256), 0, st, work, (int)(grid.x * grid.y), N * 3,
                      gcolors, total);
   return eml::check_launch("eml_sg_rasterise_bwd_colors_ex_f32(reduce)");
+}
+
+// All three gradients (see sg_rasterise_bwd_full_tiled_kernel).  work: eml_sg_rasterise_bwd_full_work_floats(B, N, H, W) floats.
+extern "C" size_t eml_sg_rasterise_bwd_full_work_floats(int B, int N, int H, int W) {
+  if (B < 1 || N < 1 || H < 1 || W < 1) return 0;
+  return (size_t)B * ((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH) * N * kSums;
+}
+
+extern "C" int eml_sg_rasterise_bwd_f32(const float* dirs, const float* sizes, const float* colors, const float* gout,
+                                        float* gdirs, float* gsizes, float* gcolors, float* work, int B, int N, int H, int W,
+                                        int flags, eml_stream_t stream) {
+  if (!dirs || !sizes || !colors || !gout || !work)
+    return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: null pointer");
+  if (!gdirs && !gsizes && !gcolors) return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: null pointer (no output requested)");
+  if (B < 0 || N < 1 || H < 1 || W != 2 * H)
+    return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: need N>=1, H>=1, W==2H (got B=%d N=%d H=%d W=%d)", B, N, H, W);
+  if (flags & ~EML_SG_EXHAUSTIVE) return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: unknown flags 0x%x", flags);
+  if (B == 0) return EML_OK;
+  if (B > 65535) return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: B=%d exceeds grid.z", B);
+  if ((long)B * N * kSums > 2147483647L) return eml::fail(EML_EINVAL, "eml_sg_rasterise_bwd_f32: too many lights");
+  const float step = (float)(3.14159265358979323846 / (double)H);
+  const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, B);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sg_rasterise_bwd_full_tiled_kernel, grid, dim3(256), 0, st, dirs, sizes, colors, gout, work, N, H, W, step,
+                     (flags & EML_SG_EXHAUSTIVE) ? 1 : 0);
+  int rc = eml::check_launch("eml_sg_rasterise_bwd_f32");
+  if (rc) return rc;
+  const int total = B * N * kSums;
+  hipLaunchKernelGGL(sg_reduce_full_kernel, dim3((total + 255) / 256), dim3(256), 0, st, work, sizes, (int)(grid.x * grid.y), N,
+                     gdirs, gsizes, gcolors, total);
+  return eml::check_launch("eml_sg_rasterise_bwd_f32(reduce)");
 }

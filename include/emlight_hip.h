@@ -36,7 +36,7 @@ typedef void* eml_stream_t; /* hipStream_t */
 
 /* Library ABI version (bumped on any signature change; the ctypes binding refuses a library built from another
  * version of this header) and last-error text. */
-#define EML_ABI_VERSION 29
+#define EML_ABI_VERSION 30
 int eml_abi_version(void);
 const char* eml_last_error(void);
 
@@ -70,6 +70,18 @@ int eml_sg_rasterise_bwd_colors_f32(const float* dirs, const float* sizes, const
 size_t eml_sg_rasterise_bwd_work_floats(int B, int N, int H, int W);
 int eml_sg_rasterise_bwd_colors_ex_f32(const float* dirs, const float* sizes, const float* gout, float* gcolors, float* work,
                                        int B, int N, int H, int W, int flags, eml_stream_t stream);
+/* All three gradients of the rasteriser (autograd of util.py:222-245 wrt dirs, sizes and colors; the reference is plain torch
+ * arithmetic, differentiable in every input).  With e = exp((d_i . xyz_hw - 1) / s_i) and q_i = sum_c gout[b,c,h,w] colors_i,c:
+ *   gcolors[b,3i+c] = sum_hw gout[b,c,h,w] e                 (bit for bit eml_sg_rasterise_bwd_colors_ex_f32's result)
+ *   gsizes[b,i]     = (1/s_i^2) sum_hw q_i e (1 - d_i . xyz_hw)
+ *   gdirs[b,3i+k]   = (1/s_i)   sum_hw q_i e xyz_k,hw          (dirs used raw: non-unit directions allowed)
+ * Same tiles, survivor lists and flags as eml_sg_rasterise_bwd_colors_ex_f32; per-tile partials in `work`
+ * (eml_sg_rasterise_bwd_full_work_floats(B, N, H, W) floats) added in tile order -- no atomics, run-to-run exact.  Any of
+ * gdirs / gsizes / gcolors may be NULL (not computed into), not all three; colors is always read. */
+size_t eml_sg_rasterise_bwd_full_work_floats(int B, int N, int H, int W);
+int eml_sg_rasterise_bwd_f32(const float* dirs, const float* sizes, const float* colors, const float* gout, float* gdirs,
+                             float* gsizes, float* gcolors, float* work, int B, int N, int H, int W, int flags,
+                             eml_stream_t stream);
 
 /* ---------------------------------------------------------------- Sinkhorn (spherical mover's loss)
  * Chord-length ground cost M_ij = ||a_i - a_j||_2 over N anchors (N x 3, f32).
