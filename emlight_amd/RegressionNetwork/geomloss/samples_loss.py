@@ -8,7 +8,14 @@ lift what the reference hard-codes: ``anchors`` (reference: 96, ``geomloss/utils
 and ``cost_matrix`` (a runtime (N,N) ground cost -- gives the GMLight variant,
 ``gmloss/utils.py:63-108``, for free).  ``batchsize`` is accepted and ignored: the chord
 matrix is stored once, not ``batchsize`` times (``utils.py:80-81``).
+
+``reach`` (unbalanced OT) follows EMLight's fork: ``rho = reach**p`` (``sinkhorn_divergence.py:35``) damps every softmin of
+the loop by ``1 / (1 + eps / rho)`` (``:43-44, 78-107``; ``eml_sinkhorn_fwd_rho_f32``), and the loss is the fork's
+``<alpha, b_x - a_x> + <beta, a_y - b_y>`` of the damped duals (``:65-69``, which ignores rho) -- not upstream geomloss's
+unbalanced divergence with its exponentially transformed dual terms.
 """
+import math
+
 import torch
 from torch.nn import Module
 
@@ -85,6 +92,23 @@ def split_watch(device):
     return _split_watches[idx]
 
 
+def reach_to_rho(reach, p):
+    """``rho = reach**p`` (sinkhorn_divergence.py:35) for a validated ``reach``, or None (balanced) for ``reach=None``.
+    ``reach`` must be a number > 0; ``float('inf')`` is accepted and gives lam = 1 (the balanced numbers)."""
+    if reach is None:
+        return None
+    try:
+        r = float(reach)
+    except (TypeError, ValueError):
+        raise ValueError("reach must be None or a number > 0, got %r" % (reach,)) from None
+    if not r > 0:   # also NaN
+        raise ValueError("reach must be None or a number > 0, got %r" % (reach,))
+    try:
+        return r ** p
+    except OverflowError:
+        return math.inf
+
+
 def sinkhorn_outputs(B, N, dev, need_gx=True, need_gy=False):
     """Device buffers one ``eml_sinkhorn_fwd_ex_f32`` call writes (the caller owns every buffer, include/emlight_hip.h)."""
     f32 = dict(dtype=torch.float32, device=dev)
@@ -116,36 +140,49 @@ def global_range(x, y):
 
 
 def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=True, need_gy=False, out=None,
-                 range_lo_hi=None, flags=None):
+                 range_lo_hi=None, flags=None, rho=None, want_lam=False):
     """One call into the HIP library; returns every device-side output (no autograd).  ``out``: buffers from
     ``sinkhorn_outputs`` to write into (a timing loop passes them so that no allocation sits between launches).
     ``range_lo_hi``: device (2,) tensor from ``global_range`` -- the kernel folds it into its own scan.
-    ``flags``: EML_SINKHORN_* of the C ABI; default: whatever the split kernel's watch says (``_SplitWatch``)."""
+    ``flags``: EML_SINKHORN_* of the C ABI; default: whatever the split kernel's watch says (``_SplitWatch``).
+    ``rho``: reach**p of unbalanced OT, or None (balanced: the call is ``eml_sinkhorn_fwd_ex_f32``, as it always was);
+    ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when balanced)."""
     L = _lib.lib()
     B, N = x.shape
     o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy)
     watched = flags is None and split_eligible(N)
     if flags is None:
         flags = split_watch(x.device).flags() if watched else 0
-    _lib.check(L.eml_sinkhorn_fwd_ex_f32(
-        _lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
-        float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
-        _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]), _lib.ptr(o["gx"]),
-        _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N, int(flags), _lib.current_stream()), "eml_sinkhorn_fwd_ex_f32")
+    args = (_lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
+            float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
+            _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]),
+            _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N, int(flags))
+    lam = None
+    if rho is None and not want_lam:
+        _lib.check(L.eml_sinkhorn_fwd_ex_f32(*args, _lib.current_stream()), "eml_sinkhorn_fwd_ex_f32")
+    else:
+        if want_lam:
+            lam = o.get("lam")
+            lam = torch.empty(64, dtype=torch.float32, device=x.device) if lam is None else lam
+        _lib.check(L.eml_sinkhorn_fwd_rho_f32(*args, float(rho) if rho is not None else 0.0, _lib.ptr(lam),
+                                              _lib.current_stream()), "eml_sinkhorn_fwd_rho_f32")
     if watched and o["work"].numel() > 24 * B * N:
         split_watch(x.device).after_call(o["work"], B, N)
-    return {"loss": o["loss"], "gx": o["gx"], "gy": o["gy"], "eps_s": o["eps_s"], "n_eps": o["n_eps"],
-            "diameter": o["diameter"], "duals": o["work"][:4 * B * N].view(4, B, N), "work": o["work"]}
+    r = {"loss": o["loss"], "gx": o["gx"], "gy": o["gy"], "eps_s": o["eps_s"], "n_eps": o["n_eps"],
+         "diameter": o["diameter"], "duals": o["work"][:4 * B * N].view(4, B, N), "work": o["work"]}
+    if lam is not None:
+        r["lam"] = lam
+    return r
 
 
 class _SinkhornDivergence(torch.autograd.Function):
     """loss (B,) = S_eps(alpha@x, beta@y).  Backward = analytic gradient of the last
-    extrapolation (``sinkhorn_divergence.py:101-107``), produced by the forward kernel."""
+    extrapolation (``sinkhorn_divergence.py:101-107``), produced by the forward kernel.  ``rho``: reach**p or None."""
 
     @staticmethod
-    def forward(ctx, x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, range_lo_hi=None):
+    def forward(ctx, x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, range_lo_hi=None, rho=None):
         r = sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter,
-                         ctx.needs_input_grad[0], ctx.needs_input_grad[1], range_lo_hi=range_lo_hi)
+                         ctx.needs_input_grad[0], ctx.needs_input_grad[1], range_lo_hi=range_lo_hi, rho=rho)
         ctx.save_for_backward(r["gx"], r["gy"])
         return r["loss"]
 
@@ -163,7 +200,7 @@ class _SinkhornDivergence(torch.autograd.Function):
             _lib.check(L.eml_sinkhorn_bwd_f32(_lib.ptr(gloss), _lib.ptr(gu), _lib.ptr(go), B, N,
                                               _lib.current_stream()), "eml_sinkhorn_bwd_f32")
             out[k] = go
-        return out[0], out[1], None, None, None, None, None, None, None, None, None
+        return out[0], out[1], None, None, None, None, None, None, None, None, None, None
 
 
 class SamplesLoss(Module):
@@ -172,6 +209,11 @@ class SamplesLoss(Module):
     ``SamplesLoss(loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5,
     batchsize=None)`` -- reference signature ``samples_loss.py:22``; ``forward(x, y)`` with
     ``x, y`` of shape ``(B, N, 1)`` returns ``(B,)`` (``samples_loss.py:35-46``).
+
+    ``reach``: None (balanced OT) or a number > 0 (``float('inf')`` included; anything else raises ``ValueError``).
+    With a reach, every softmin of the Sinkhorn loop is damped by ``1 / (1 + eps / reach**p)`` as in EMLight's fork
+    (``sinkhorn_divergence.py:35, 43-44, 78-107``); the loss stays the fork's ``<alpha, b_x - a_x> + <beta, a_y - b_y>``
+    of the damped duals (``:65-69``), NOT upstream geomloss's unbalanced divergence.
     """
 
     def __init__(self, loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5,
@@ -179,8 +221,7 @@ class SamplesLoss(Module):
         super().__init__()
         if loss != "sinkhorn":
             raise ValueError("only loss='sinkhorn' exists in EMLight's geomloss fork")
-        if reach is not None:
-            raise NotImplementedError("unbalanced OT (reach) is not on EMLight's path (rho=None)")
+        self.rho = reach_to_rho(reach, p)   # validates reach
         self.loss, self.p, self.blur, self.reach = loss, p, blur, reach
         self.diameter, self.scaling = diameter, scaling
         # data-parallel training: derive the eps-schedule from the range of the GLOBAL batch (one 2-float all-reduce per
@@ -242,14 +283,15 @@ class SamplesLoss(Module):
         b2 = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
         M, Mt = self.cost_matrix(x2.device)
         rng = global_range(x2, y2) if (self.sync_diameter and self.diameter is None) else None
-        return _SinkhornDivergence.apply(x2, y2, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng)
+        return _SinkhornDivergence.apply(x2, y2, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
 
-    def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None):
-        """Every device output of one call (loss, unit grads, schedule, duals) -- for parity tests and timing."""
+    def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None, want_lam=False):
+        """Every device output of one call (loss, unit grads, schedule, duals; with ``want_lam`` the dampening schedule
+        ``lam`` next to ``eps_s``) -- for parity tests and timing."""
         B = x.shape[0]
         x2 = _lib.require_gpu_tensor(x.reshape(B, self.N), "x")
         y2 = _lib.require_gpu_tensor(y.reshape(B, self.N), "y")
         M, Mt = self.cost_matrix(x2.device)
         rng = global_range(x2, y2) if (self.sync_diameter and self.diameter is None) else None
         return sinkhorn_raw(x2, y2, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
-                            need_gx, need_gy, out, range_lo_hi=rng, flags=flags)
+                            need_gx, need_gy, out, range_lo_hi=rng, flags=flags, rho=self.rho, want_lam=want_lam)

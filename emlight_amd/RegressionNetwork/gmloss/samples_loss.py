@@ -33,7 +33,8 @@ def geometric_points(n=128, anchor_depth=None):
 class SamplesLoss(_SphereSamplesLoss):
     """``SamplesLoss(loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5, batchsize=None)``,
     ``forward(x, y, geometry) -> (B,)`` with x, y of shape (B, 128, 1).  ``anchors`` lifts the reference's hard-coded
-    N = 128 (``gmloss/utils.py:78``)."""
+    N = 128 (``gmloss/utils.py:78``).  ``reach`` (unbalanced OT, the fork's damped loop and loss) works as in
+    ``geomloss.SamplesLoss``: ``forward`` runs the parent's, which passes ``reach**p`` to the kernel."""
 
     def __init__(self, loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5, batchsize=None,
                  anchors=128):

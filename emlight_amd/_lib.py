@@ -16,7 +16,7 @@ _f64p = ctypes.c_void_p
 _stream = ctypes.c_void_p
 _int = ctypes.c_int
 
-ABI_VERSION = 30   # == EML_ABI_VERSION of include/emlight_hip.h
+ABI_VERSION = 31   # == EML_ABI_VERSION of include/emlight_hip.h
 
 # symbol -> (restype, argtypes): exactly the declarations of include/emlight_hip.h
 SIGNATURES = {
@@ -35,6 +35,9 @@ SIGNATURES = {
     "eml_sinkhorn_fwd_ex_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_double, ctypes.c_double, _int,
                                        ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
                                        _int, _stream]),
+    "eml_sinkhorn_fwd_rho_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_double, ctypes.c_double, _int,
+                                        ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
+                                        _int, ctypes.c_double, _f32p, _stream]),
     "eml_sinkhorn_bwd_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _stream]),
     # the generator's L1-type loss terms (host pointer arrays: ctypes arrays of c_void_p / c_long / c_int / c_float)
     "eml_l1_pairs_partial_doubles": (ctypes.c_size_t, [_int]),

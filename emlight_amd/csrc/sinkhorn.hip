@@ -73,7 +73,9 @@ constexpr int kSmemVecs = 2 + 2 + 4 + 2;
 
 // ---- epsilon schedule, computed by every workgroup (no separate launch, no host sync):
 // d = diameter > 0 ? diameter : range(x U y) over the WHOLE batch (sinkhorn_divergence.py:9-18),
-// eps_s = [d^p] + [exp(e) for e in arange(p ln d, p ln blur, p ln scaling)] + [blur^p] in f64 like numpy
+// eps_s = [d^p] + [exp(e) for e in arange(p ln d, p ln blur, p ln scaling)] + [blur^p] in f64 like numpy, and next to each
+// entry the dampening lam_k = 1 / (1 + eps_k / rho) of unbalanced OT (sinkhorn_divergence.py:35,43-44; rho = reach^p <= 0:
+// balanced, lam_k = 1 exactly), formed in f64 from the f64 eps_k and rounded to f32 once -- as the reference's Python float
 // The scan's first trip (four float4 per thread) is a separate step so that a kernel can REQUEST it early and do other
 // work (staging) while it is in flight: schedule_scan_begin issues the loads, device_schedule folds them.
 struct ScanHead {
@@ -108,9 +110,9 @@ template <int kWG, bool kFinalBarrier = true>
 __device__ __forceinline__ void device_schedule(const ScanHead& head, const float* __restrict__ x,
                                                 const float* __restrict__ y, int B, int N,
                                                 double blur, double log_blur, double log_scaling, int p_exp,
-                                                double diameter, float* eps_l,
+                                                double diameter, double rho, float* eps_l, float* lam_l,
                                                 int* n_eps_l, float* __restrict__ eps_out, int* __restrict__ n_eps_out,
-                                                float* __restrict__ diameter_out) {
+                                                float* __restrict__ diameter_out, float* __restrict__ lam_out) {
   __shared__ float red_lo[16], red_hi[16];
   const int tid0 = threadIdx.x;
   float lo = INFINITY, hi = -INFINITY;
@@ -173,8 +175,11 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
       if (tid0 == 0) e = (p_exp == 2) ? d * d : pow(d, (double)p_exp);
       else if (tid0 == cnt + 1) e = (p_exp == 2) ? blur * blur : pow(blur, (double)p_exp);
       else e = exp(start + (tid0 - 1) * step);
+      const float lam = (rho > 0.0) ? (float)(1.0 / (1.0 + e / rho)) : 1.0f;
       eps_l[tid0] = (float)e;
+      lam_l[tid0] = lam;
       if (blockIdx.x == 0 && eps_out) eps_out[tid0] = (float)e;
+      if (blockIdx.x == 0 && lam_out) lam_out[tid0] = lam;
     }
     if (tid0 == 0) {
       *n_eps_l = cnt + 2;
@@ -184,7 +189,7 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
       }
     }
   }
-  if (kFinalBarrier) __syncthreads();   // otherwise the caller's next barrier publishes eps_l / n_eps_l
+  if (kFinalBarrier) __syncthreads();   // otherwise the caller's next barrier publishes eps_l / lam_l / n_eps_l
 }
 
 // threads per softmin group: cached kernel 512 (128 rows x 4 lanes), stream kernel 256 (row per thread)
@@ -193,11 +198,12 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ M,
     const float* __restrict__ Mt, const float* __restrict__ alpha, const float* __restrict__ beta,
     double blur, double log_blur, double log_scaling, int p_exp, double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out,
-    int* __restrict__ n_eps_out, float* __restrict__ diameter_out,
+    int* __restrict__ n_eps_out, float* __restrict__ diameter_out, double rho, float* __restrict__ lam_out,
     float* __restrict__ work /* (8,B,N): duals a_x,b_y,a_y,b_x then E rows */, int B, int N) {
   constexpr int kGT = kCached ? 512 : 256;  // threads per softmin group
   constexpr int kWG = 2 * kGT;              // two groups per workgroup
   __shared__ float eps_l[EML_MAX_EPS];
+  __shared__ float lam_l[EML_MAX_EPS];
   __shared__ int n_eps_l;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int NP = round_up4(N) + kJPT;
@@ -276,8 +282,8 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     }
     EML_STAMP(1);   // this thread's staging written
   }
-  device_schedule<kWG, !kCached>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, eps_l, &n_eps_l, eps_out, n_eps_out,
-                                 diameter_out);
+  device_schedule<kWG, !kCached>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, rho, eps_l, lam_l, &n_eps_l,
+                                 eps_out, n_eps_out, diameter_out, lam_out);
   const float* eps_s = eps_l;
 
   // ---- stream kernel: stage points and log-weights; h buffer 0 = log w of each group's columns, buffer 1 zeroed
@@ -349,7 +355,11 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
   float pot = 0.f;  // this row's potential (cached kernel)
   for (int s = 0; s < n_eps + 2; ++s) {
     const bool final_sweep = (s == n_eps + 1);
-    const float eps = eps_s[(s == 0) ? 0 : min(s - 1, n_eps - 1)];
+    const int k_eps = (s == 0) ? 0 : min(s - 1, n_eps - 1);
+    const float eps = eps_s[k_eps];
+    // -eps * lam_k: the dampening multiplies the softmin before the symmetrised average and before any fold
+    // (sinkhorn_divergence.py:82-93,102-107); with lam_k = 1 the product is -eps itself, bit for bit
+    const float neg_eps_lam = -eps * lam_l[k_eps];
     const float eps_next = eps_s[min(s, n_eps - 1)];
     const float nie2 = -kLog2e / eps;
     const float k_next = kLog2e / eps_next;
@@ -405,12 +415,12 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
       }
       sum += eml::lane_xor1(sum);
       sum += eml::lane_xor2(sum);
-      // softmin = -eps * logsumexp (samples_loss.py:75-77), evaluated in base 2
-      const float sm = -eps * kLn2 * (m + __builtin_amdgcn_logf(sum));
+      // lam * softmin = -eps * lam * logsumexp (samples_loss.py:75-77, sinkhorn_divergence.py:90-93), evaluated in base 2
+      const float sm = neg_eps_lam * kLn2 * (m + __builtin_amdgcn_logf(sum));
       if (final_sweep) {
         if (owner) {
           fin_out[i] = sm;
-          e_out[i] = tq / sum;
+          e_out[i] = lam_l[k_eps] * (tq / sum);   // lam_last-scaled expectation row: the gradient of lam * softmin
         }
       } else {
         pot = (s == 0) ? sm : 0.5f * (pot + sm);  // symmetrised update, sinkhorn_divergence.py:96-97
@@ -432,10 +442,10 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
           sum += e;
           tq = fmaf(e, qj, tq);
         }
-        const float sm = -eps * kLn2 * (m + __builtin_amdgcn_logf(sum));
+        const float sm = neg_eps_lam * kLn2 * (m + __builtin_amdgcn_logf(sum));
         if (final_sweep) {
           fin_out[r] = sm;
-          e_out[r] = tq / sum;
+          e_out[r] = lam_l[k_eps] * (tq / sum);
         } else {
           const float pr = (s == 0) ? sm : 0.5f * (potl[gl * NP + r] + sm);
           potl[gl * NP + r] = pr;
@@ -460,7 +470,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
     const float* __restrict__ alpha, const float* __restrict__ beta, double blur, double log_blur, double log_scaling,
     int p_exp,
     double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out, int* __restrict__ n_eps_out, float* __restrict__ diameter_out,
-    float* __restrict__ work, int B, int N, const int* __restrict__ only_if) {
+    double rho, float* __restrict__ lam_out, float* __restrict__ work, int B, int N, const int* __restrict__ only_if) {
   // `only_if` (device, may be NULL): the RESCUE launch behind the split kernel -- it returns at once unless the split
   // kernel raised its status word (a slice never saw its partners), in which case it recomputes the whole batch here
   if (only_if && __hip_atomic_load(only_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -469,9 +479,10 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
   constexpr int TJ = 16 * LPR;             // tile columns; every lane folds 16 of them
   constexpr int TS = TJ + 4;               // LDS row stride of a tile
   __shared__ float eps_l[EML_MAX_EPS];
+  __shared__ float lam_l[EML_MAX_EPS];
   __shared__ int n_eps_l;
   device_schedule<kWG>(schedule_scan_begin<kWG>(x, y, B, N, diameter, range_dev), x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter,
-                       eps_l, &n_eps_l, eps_out, n_eps_out, diameter_out);
+                       rho, eps_l, lam_l, &n_eps_l, eps_out, n_eps_out, diameter_out, lam_out);
   const float* eps_s = eps_l;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int NP = round_up4(N) + kJPT;
@@ -545,7 +556,11 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
   int buf = 0;
   for (int s = 0; s < n_eps + 2; ++s) {
     const bool final_sweep = (s == n_eps + 1);
-    const float eps = eps_s[(s == 0) ? 0 : min(s - 1, n_eps - 1)];
+    const int k_eps = (s == 0) ? 0 : min(s - 1, n_eps - 1);
+    const float eps = eps_s[k_eps];
+    // -eps * lam_k: the dampening multiplies the softmin before the symmetrised average and before any fold
+    // (sinkhorn_divergence.py:82-93,102-107); with lam_k = 1 the product is -eps itself, bit for bit
+    const float neg_eps_lam = -eps * lam_l[k_eps];
     const float eps_next = eps_s[min(s, n_eps - 1)];
     const float nie2 = -kLog2e / eps, k_next = kLog2e / eps_next;
     const float* hsrc = h2 + (s & 1) * 2 * NP + gl * NP;
@@ -618,11 +633,11 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
       tq = tq_run * fa + qo * fb;
     }
     const float row_shift = 0.05f * nie2 * pi * pi;   // the row-only term of the exponents, left out of the tiles above
-    const float sm = -eps * kLn2 * ((m + row_shift) + __builtin_amdgcn_logf(sum));
+    const float sm = neg_eps_lam * kLn2 * ((m + row_shift) + __builtin_amdgcn_logf(sum));
     if (final_sweep) {
       if (owner) {
         fin_out[i] = sm;
-        e_out[i] = tq / sum;
+        e_out[i] = lam_l[k_eps] * (tq / sum);
       }
     } else {
       pot = (s == 0) ? sm : 0.5f * (pot + sm);
@@ -662,11 +677,12 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ M,
     const float* __restrict__ alpha, const float* __restrict__ beta, double blur, double log_blur, double log_scaling,
     int p_exp, double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out,
-    int* __restrict__ n_eps_out, float* __restrict__ diameter_out, float* __restrict__ work,
-    unsigned long long* __restrict__ exch, int B, int S, int* __restrict__ status, int test_stall) {
+    int* __restrict__ n_eps_out, float* __restrict__ diameter_out, double rho, float* __restrict__ lam_out,
+    float* __restrict__ work, unsigned long long* __restrict__ exch, int B, int S, int* __restrict__ status, int test_stall) {
   constexpr int N = CPL * kSplitLPR, kWG = 16 * R, kGT = 8 * R, LDM = N + 32;   // LDM = 32 mod 64: two rows cover all banks
   static_assert(CPL % 4 == 0 && N % 64 == 0 && kWG <= 1024, "split kernel geometry");
   __shared__ float eps_l[EML_MAX_EPS];
+  __shared__ float lam_l[EML_MAX_EPS];
   __shared__ int n_eps_l;
   __shared__ int failed_l;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -704,9 +720,9 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
     const int e = tid + k * kWG, row = e / (N / 4), c4 = e % (N / 4);
     *reinterpret_cast<float4*>(Ml + row * LDM + 4 * c4) = mreg[k];
   }
-  device_schedule<kWG>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, eps_l, &n_eps_l,
+  device_schedule<kWG>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, rho, eps_l, lam_l, &n_eps_l,
                        (slice == 0) ? eps_out : nullptr, (slice == 0) ? n_eps_out : nullptr,
-                       (slice == 0) ? diameter_out : nullptr);   // ends with a barrier: LDS staging above is visible
+                       (slice == 0) ? diameter_out : nullptr, (slice == 0) ? lam_out : nullptr);   // ends with a barrier: LDS staging above is visible
   const float* eps_s = eps_l;
   const int n_eps = n_eps_l;
   if (failed_l) return;   // workgroup-uniform (read after a barrier): the rescue launch recomputes the batch
@@ -737,7 +753,11 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
   float pot = 0.f;
   for (int s = 0; s < n_eps + 2; ++s) {
     const bool final_sweep = (s == n_eps + 1);
-    const float eps = eps_s[(s == 0) ? 0 : min(s - 1, n_eps - 1)];
+    const int k_eps = (s == 0) ? 0 : min(s - 1, n_eps - 1);
+    const float eps = eps_s[k_eps];
+    // -eps * lam_k: the dampening multiplies the softmin before the symmetrised average and before any fold
+    // (sinkhorn_divergence.py:82-93,102-107); with lam_k = 1 the product is -eps itself, bit for bit
+    const float neg_eps_lam = -eps * lam_l[k_eps];
     const float eps_next = eps_s[min(s, n_eps - 1)];
     const float nie2 = -kLog2e / eps, k_next = kLog2e / eps_next;
     const float* hsrc = h2 + (s & 1) * 2 * N + gl * N;
@@ -802,14 +822,14 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
     sum += eml::lane_xor2(sum);
     sum += eml::dpp_mov<0x141>(sum);
     const float row_shift = 0.05f * nie2 * pi * pi;
-    const float sm = -eps * kLn2 * ((m + row_shift) + __builtin_amdgcn_logf(sum));
+    const float sm = neg_eps_lam * kLn2 * ((m + row_shift) + __builtin_amdgcn_logf(sum));
     if (final_sweep) {
       tq += eml::lane_xor1(tq);
       tq += eml::lane_xor2(tq);
       tq += eml::dpp_mov<0x141>(tq);
       if (owner) {
         fin_out[i] = sm;
-        e_out[i] = tq / sum;
+        e_out[i] = lam_l[k_eps] * (tq / sum);
       }
       break;
     }
@@ -863,7 +883,8 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
 // loss_b = <alpha, b_x - a_x> + <beta, a_y - b_y>  (sinkhorn_divergence.py:65-69) and the
 // analytic backward of the last extrapolation: the gradient reaches x only through the final
 // xx / xy softmins and only through the cost's first argument (utils.py:88), and since the
-// softmax rows sum to one,  dL_b/dx_i = alpha_i * 0.1 * (E^xx_i[x] - E^xy_i[y])  (same for y).
+// softmax rows sum to one,  dL_b/dx_i = alpha_i * 0.1 * (E^xx_i[x] - E^xy_i[y])  (same for y).  Unbalanced OT multiplies
+// the last extrapolation by lam_last: the loop kernels' final sweep stores the E rows already scaled by it (1 when balanced).
 __global__ __launch_bounds__(256) void sinkhorn_finish_kernel(
     const float* __restrict__ work, const float* __restrict__ alpha, const float* __restrict__ beta,
     float* __restrict__ loss, float* __restrict__ gx, float* __restrict__ gy, int B, int N) {
@@ -1036,20 +1057,21 @@ size_t split_lds_bytes(int N, int R) { return (size_t)(10 * N + R * (N + 32)) * 
 // `only_if`: see the kernel (the rescue launch behind the split kernel).
 void launch_tiled(const float* x, const float* y, const float* M, const float* alpha, const float* beta, double blur,
                   double log_blur, double log_scaling, int p, double diameter, const float* range_lo_hi, float* eps_out,
-                  int* n_eps_out, float* diameter_out, float* work, int B, int N, const int* only_if, hipStream_t stream) {
+                  int* n_eps_out, float* diameter_out, double rho, float* lam_out, float* work, int B, int N,
+                  const int* only_if, hipStream_t stream) {
   const int NP = round_up4(N) + kJPT;
   const int lpr = N <= 256 ? 2 : 1;
   const size_t lds = (size_t)(10 * NP + 2 * (512 / lpr) * (16 * lpr + 4)) * sizeof(float);
   if (lpr == 2) {
     EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<2>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<2>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
-                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, work, B, N,
-                       only_if);
+                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
+                       B, N, only_if);
   } else {
     EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<1>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<1>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
-                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, work, B, N,
-                       only_if);
+                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
+                       B, N, only_if);
   }
 }
 
@@ -1102,6 +1124,19 @@ extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const flo
                                        double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
                                        float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                                        int flags, eml_stream_t stream) {
+  return eml_sinkhorn_fwd_rho_f32(x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
+                                  diameter_out, loss, gx, gy, work, B, N, flags, 0.0, nullptr, stream);
+}
+
+// rho = reach^p > 0: every softmin of the loop is damped by lam_k = 1 / (1 + eps_k / rho) (the kernels' lam_l); rho <= 0
+// (and rho = +inf) give lam_k = 1 and the balanced outputs bit for bit.  The finishing kernel is unchanged: the loss reads
+// the damped duals, and the final sweep stores the expectation rows already scaled by lam_last.
+extern "C" int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const float* M, const float* Mt,
+                                        const float* alpha, const float* beta, double blur, double scaling, int p,
+                                        double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                                        float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                                        int flags, double rho, float* lam_out, eml_stream_t stream) {
+  if (std::isnan(rho)) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_rho_f32: rho is NaN");
   if (!x || !y || !M || !Mt || !loss || !work) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: null pointer");
   if (flags & ~(EML_SINKHORN_NO_SPLIT | EML_SINKHORN_FORCE_SPLIT | EML_SINKHORN_TEST_STALL))
     return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_ex_f32: unknown flags 0x%x", flags);
@@ -1118,7 +1153,7 @@ extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const flo
     EML_ENSURE_LDS((&sinkhorn_loop_kernel<true>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_kernel<true>, dim3(2 * B), dim3(1024), lds, (hipStream_t)stream, x, y, M, Mt,
                        alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       work, B, N);
+                       rho, lam_out, work, B, N);
   } else if (N <= 512 && (N & 63) == 0 && N >= 192 && !(flags & EML_SINKHORN_NO_SPLIT) &&
              (split_s = split_slices(B, N, flags, (hipStream_t)stream)) > 0) {
     // small batch: the rows of every problem pair split over S workgroups (one per CU, all resident), duals exchanged
@@ -1136,7 +1171,7 @@ extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const flo
     EML_ENSURE_LDS((&sinkhorn_loop_split_kernel<CPLV, RV>), lds);                                                      \
     hipLaunchKernelGGL((sinkhorn_loop_split_kernel<CPLV, RV>), dim3(2 * B * S), dim3(16 * RV), lds, (hipStream_t)stream, \
                        x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, \
-                       diameter_out, work, exch, B, S, status, (flags & EML_SINKHORN_TEST_STALL) ? 1 : 0);              \
+                       diameter_out, rho, lam_out, work, exch, B, S, status, (flags & EML_SINKHORN_TEST_STALL) ? 1 : 0); \
   } while (0)
     if (N == 256 && S == 8) EML_LAUNCH_SPLIT(32, 32);
     else if (N == 256) EML_LAUNCH_SPLIT(32, 64);
@@ -1151,15 +1186,15 @@ extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const flo
     if (rcs) return rcs;
     // the rescue: the tiled kernel, gated on the status word -- returns at once unless a slice gave up
     launch_tiled(x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                 diameter_out, work, B, N, status, (hipStream_t)stream);
+                 diameter_out, rho, lam_out, work, B, N, status, (hipStream_t)stream);
   } else if (N <= 512 && (N & 3) == 0) {
     launch_tiled(x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                 diameter_out, work, B, N, nullptr, (hipStream_t)stream);
+                 diameter_out, rho, lam_out, work, B, N, nullptr, (hipStream_t)stream);
   } else {
     EML_ENSURE_LDS((&sinkhorn_loop_kernel<false>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_kernel<false>, dim3(2 * B), dim3(512), lds, (hipStream_t)stream, x, y, M, Mt,
                        alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       work, B, N);
+                       rho, lam_out, work, B, N);
   }
   int rc = eml::check_launch("eml_sinkhorn_fwd_f32(loop)");
   if (rc) return rc;

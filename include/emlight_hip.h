@@ -36,7 +36,7 @@ typedef void* eml_stream_t; /* hipStream_t */
 
 /* Library ABI version (bumped on any signature change; the ctypes binding refuses a library built from another
  * version of this header) and last-error text. */
-#define EML_ABI_VERSION 30
+#define EML_ABI_VERSION 31
 int eml_abi_version(void);
 const char* eml_last_error(void);
 
@@ -152,6 +152,23 @@ int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const float* M, cons
                             double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
                             float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                             int flags, eml_stream_t stream);
+
+/* The same call with unbalanced OT (ABI 31): SamplesLoss(reach=...), rho = reach^p (sinkhorn_divergence.py:35).  Every
+ * softmin of the loop -- init sweep, eps-scaling sweeps, last extrapolation -- is multiplied by the dampening
+ * lam_k = 1 / (1 + eps_k / rho) of its schedule entry (sinkhorn_divergence.py:43-44, 78-107), formed in f64 from the f64
+ * eps_k and rounded to f32 once; the symmetrised averaging is unchanged.  The loss keeps EMLight's fork formula
+ * <alpha,b_x-a_x> + <beta,a_y-b_y> of the damped duals (:65-69, which ignores rho -- NOT upstream geomloss's unbalanced
+ * divergence), and gx / gy are the analytic gradients of the damped last extrapolation (lam_last times the balanced form;
+ * the expectation rows in work are stored already scaled by lam_last).
+ *   rho      reach^p; rho <= 0 (or +inf) is balanced: lam_k = 1 and the outputs of eml_sinkhorn_fwd_ex_f32, bit for bit
+ *   lam_out  device float[EML_MAX_EPS] receiving lam_k next to eps_out, or NULL
+ * Every other argument, the flags, the split path and its rescue launch (which is passed the same rho) are as
+ * eml_sinkhorn_fwd_ex_f32, which forwards here with rho = 0. */
+int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const float* M, const float* Mt,
+                             const float* alpha, const float* beta, double blur, double scaling, int p,
+                             double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                             float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                             int flags, double rho, float* lam_out, eml_stream_t stream);
 
 /* Backward of the loss vector: gout[b,i] = gloss[b] * gunit[b,i]  (gunit = gx or gy above). */
 int eml_sinkhorn_bwd_f32(const float* gloss, const float* gunit, float* gout, int B, int N,

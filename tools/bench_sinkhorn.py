@@ -1,6 +1,76 @@
-import sys, os
+#!/usr/bin/env python
+"""GPU microseconds per Sinkhorn loss call (SamplesLoss.forward_raw: loop kernel + finishing kernel, forward and both unit
+gradients), balanced and with a ``--reach`` (unbalanced OT, eml_sinkhorn_fwd_rho_f32).
+
+Outputs are pre-allocated once, so a window is back-to-back launches between two HIP events on torch's current stream; the
+balanced and the damped call alternate window by window in the same process, and a figure is the median over `--windows`
+windows of `--reps` calls.  Shapes: cfg2 (B=64, N=128, the register-resident kernel) and cfg5 per GPU (B=16, N=256, the
+split kernel), blur .05, the inputs of bench.py's Sinkhorn leg.
+
+    python tools/bench_sinkhorn.py [--reach .1] [--reps 200] [--windows 7] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench
-for B in (64, 256):
-    r = bench.time_sinkhorn(B, 128, .05, "cuda:0", reps=50)
-    print(B, r["ms_per_loss_call"], r["sweeps"], r["ms_per_eps_step"], r["frac_of_hbm_peak_8TBps"])
+
+SHAPES = [("cfg2", 64, 128), ("cfg5_per_gpu", 16, 256)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reach", type=float, default=.1, help="reach of the damped calls (SamplesLoss(reach=...))")
+    ap.add_argument("--blur", type=float, default=.05)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_sinkhorn.py needs the MI355X")
+    from emlight_amd.RegressionNetwork.geomloss import SamplesLoss
+    from emlight_amd.RegressionNetwork.geomloss.samples_loss import sinkhorn_outputs
+    dev = torch.device("cuda:0")
+    rows = []
+    for name, B, N in SHAPES:
+        g = torch.Generator().manual_seed(7)
+        x = torch.softmax(torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
+        y = torch.softmax(3 * torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
+        calls = {}
+        for label, reach in (("balanced", None), ("reach", a.reach)):
+            crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, reach=reach, anchors=N)
+            out = sinkhorn_outputs(B, N, dev, True, True)
+            calls[label] = (lambda crit=crit, out=out: crit.forward_raw(x, y, out=out))
+        n_eps = int(calls["balanced"]()["n_eps"].item())
+        for fn in calls.values():
+            for _ in range(20):
+                fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        us = {k: [] for k in calls}
+        for _ in range(a.windows):
+            for k, fn in calls.items():
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[k].append(1e3 * e0.elapsed_time(e1) / a.reps)
+        row = {"shape": name, "B": B, "N": N, "n_eps": n_eps, "reach": a.reach}
+        for k, v in us.items():
+            row[k + "_us"] = round(float(np.median(v)), 2)
+            row[k + "_us_min_max"] = [round(float(min(v)), 2), round(float(max(v)), 2)]
+        row["reach_over_balanced"] = round(row["reach_us"] / row["balanced_us"], 4)
+        rows.append(row)
+        print(json.dumps(row))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
