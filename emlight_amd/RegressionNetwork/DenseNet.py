@@ -19,6 +19,11 @@ Supported configuration of the HIP engine: ``growth_rate=12``, ``bn_size=4`` (EM
 constructor defaults), ``drop_rate=0``, any ``block_config`` whose widest block has at most 368
 channels (3 x 16 layers: 216 / 300 / 342); backward needs train-mode BatchNorm (EMLight trains
 and tests in train mode).  Anything else raises in the constructor or at the first call.
+
+Differentiable, like the reference's stock-op module, in the input image and in every parameter,
+in any combination: ``x.requires_grad`` alone (frozen weights: a lighting-consistency loss,
+test-time optimisation of the input, saliency) gives ``x.grad``; frozen parameters get no
+``.grad``.  One backward per forward (no ``retain_graph``, no double backward).
 """
 import math
 from collections import OrderedDict

@@ -134,10 +134,14 @@ class _PermuteTable:
 
 
 class _EncoderFn(torch.autograd.Function):
+    """Differentiable in the input image and in every parameter, in any combination (train-mode BatchNorm).  Frozen
+    parameters get no gradient; the backward still runs their weight-gradient kernels (the data passes ride on them) into
+    scratch.  One backward per graph: retain_graph and double backward are refused."""
+
     @staticmethod
     def forward(ctx, enc, x, *params):
         ctx.enc = enc
-        needs_grad = any(ctx.needs_input_grad[2:])
+        needs_grad = any(ctx.needs_input_grad[1:])
         ws, pooled = enc.run_forward(x, keep_all=needs_grad)
         ctx.ws = ws
         if needs_grad:   # the buffers now belong to this graph until its backward ran (or the graph is dropped)
@@ -153,15 +157,19 @@ class _EncoderFn(torch.autograd.Function):
             raise RuntimeError("HIP DenseNet: the activations of this forward are gone -- backward() was already run on "
                                "this graph (the workspace is released after the first backward; retain_graph / double "
                                "backward are not supported)")
-        grads = ctx.enc.run_backward(ws, x, gpooled.contiguous())
+        need_x, need_params = ctx.needs_input_grad[1], ctx.needs_input_grad[2:]
+        dx, grads = ctx.enc.run_backward(ws, x, gpooled.contiguous(), need_x, need_params)
         # the buffers go back to the pool: a second backward on this graph (retain_graph=True) raises above instead of
         # reading activations a later forward may have overwritten
         ws.done, ws.owner = True, None
         ctx.enc.trim_pool(ws)
-        return (None, None) + tuple(grads)
+        return (None, dx) + tuple(g if need else None for g, need in zip(grads, need_params))
 
 
 class HipDenseEncoder:
+    """The encoder's HIP forward and backward.  ``enc(x)`` is differentiable in ``x`` and in every parameter of
+    ``param_list()``, in any combination (train-mode BatchNorm; eval mode has no backward): ``x``'s gradient is one more
+    launch after conv0's weight gradient, made only when ``x`` asks for it."""
     GRID_MAX = 1024   # upper bound of every persistent grid (scratch buffers are sized for it)
 
     @staticmethod
@@ -444,6 +452,8 @@ class HipDenseEncoder:
         return ws, pooled
 
     # ------------------------------------------------------------------ backward
-    def run_backward(self, ws, x, gpooled):
+    def run_backward(self, ws, x, gpooled, need_x=False, need_params=None):
+        """(dL/dx or None, [dL/dp for every parameter of param_list()]); need_params: per-parameter flags (None: all) --
+        the gradients of the others are written into scratch."""
         from .dense_engine_bwd import run_backward
-        return run_backward(self, ws, x, gpooled)
+        return run_backward(self, ws, x, gpooled, need_x, need_params)

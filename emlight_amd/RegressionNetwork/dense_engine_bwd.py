@@ -105,21 +105,24 @@ class _BwdBuffers:
             self.ev_done = [None] * self.ring
 
 
-def run_backward(enc, ws, x, gpooled):
+def run_backward(enc, ws, x, gpooled, need_x=False, need_params=None):
+    """need_x: also form dL/dx (eml_dense_conv0_bwd_data_f32, after every launch of a parameters-only backward).
+    need_params: per-parameter flags of enc.param_list() (None: all).  The weight-gradient kernels run for every parameter --
+    the data passes ride on them -- and write those nobody asked for into scratch, which takes no gradient-bucket slot."""
     if getattr(ws, "bwd", None) is None:
         ws.bwd = _BwdBuffers(enc, ws, x.device)
     masked = getattr(ws.bwd, "main_masked", None)
     if masked is None:
-        return _run_backward(enc, ws, x, gpooled)
+        return _run_backward(enc, ws, x, gpooled, need_x, need_params)
     cur = torch.cuda.current_stream(x.device)
     masked.wait_stream(cur)
     with torch.cuda.stream(masked):
-        out = _run_backward(enc, ws, x, gpooled)
+        out = _run_backward(enc, ws, x, gpooled, need_x, need_params)
     cur.wait_stream(masked)
     return out
 
 
-def _run_backward(enc, ws, x, gpooled):
+def _run_backward(enc, ws, x, gpooled, need_x, need_params):
     L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
     m = enc.model
     f = m.features
@@ -158,10 +161,12 @@ def _run_backward(enc, ws, x, gpooled):
                       tr_["Kp"], tr_["Ko"]))
     bw.permutes.launch(L, st, items)
     params = enc.param_list()
+    if need_params is None:
+        need_params = [True] * len(params)
     from .._dist import grad_slot
     grads = {}
-    for q in params:   # data-parallel runs: the kernels write straight into the all-reduce bucket (no packing copy)
-        slot = grad_slot(q)
+    for q, need in zip(params, need_params):   # data-parallel runs: the kernels write straight into the all-reduce bucket
+        slot = grad_slot(q) if need else None    # (no packing copy); a frozen parameter's gradient goes to scratch
         grads[id(q)] = slot if slot is not None else torch.empty_like(q)
     gr = lambda q: p(grads[id(q)])
     coefs = [tuple(bw.coef[3 * k + i] for i in range(3)) for k in range(2)]
@@ -390,6 +395,13 @@ def _run_backward(enc, ws, x, gpooled):
         _lib.check(L.eml_dense_conv0_bwd_weight_f32(p(x), p(dY), ld_dy, p(b0["X"]), b0["ld"], p(ws.Y0), c0, p(cA), p(cB),
                                                     p(cC), B, H, W, p(bw.partW), gr(f.conv0.weight), G, st),
                    "eml_dense_conv0_bwd_weight_f32")
+    dx = None
+    if need_x:   # conv0's data gradient from the same dY0 (rebuilt, not stored) the weight gradient above used
+        dx = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+        X1 = (None, 0) if norm0_fused else (p(b0["X"]), b0["ld"])
+        _lib.check(L.eml_dense_conv0_bwd_data_f32(p(dY), ld_dy, *X1, p(ws.Y0), c0, p(ws.scale0), p(ws.shift0), p(sB), p(sC),
+                                                  p(cA), p(cB), p(cC), p(f.conv0.weight), B, H, W, p(dx), st),
+                   "eml_dense_conv0_bwd_data_f32")
     if bw.side is not None:
         main.wait_stream(bw.side)   # every dW2 is complete before the gradients leave
-    return [grads[id(q)] for q in params]
+    return dx, [grads[id(q)] for q in params]

@@ -184,6 +184,8 @@ SIGNATURES = {
                                                     _int, _int, _int, _f32p, _f32p, _int, _stream]),
     "eml_dense_conv0_bwd_weight_f32": (_int, [_f32p, _f32p, _int, _f32p, _int, _f32p, _int, _f32p, _f32p, _f32p,
                                               _int, _int, _int, _f32p, _f32p, _int, _stream]),
+    "eml_dense_conv0_bwd_data_f32": (_int, [_f32p, _int, _f32p, _int, _f32p, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                            _f32p, _f32p, _int, _int, _int, _f32p, _stream]),
     "eml_dense_head_pool_bwd_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, _int, _f32p, _int, _stream]),
 }
 

@@ -2817,6 +2817,116 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(
       for (int g = 0; g < 4; ++g) out[(16 * i + 4 * kk + g) * 32 + 16 * n + r] = acc[i][n][g];
 }
 
+// =============================================================================== conv0 backward: data
+// dX[b][c][h][w] = sum_{o<24, ky, kx} W0[o][c][ky][kx] * dY0[b][h+1-ky][w+1-kx][o]: the transposed 3x3 / pad 1 convolution
+// 24 -> 3 (DenseNet.py:88-93 under autograd).  dY0 is never stored: every halo pixel of a tile rebuilds it once, into LDS, with
+// exactly conv0_bwd_weight_kernel's expression for the same path, so the input gradient is the VJP of the dY0 that dW0 used.
+// Tile: kC0dTH x kC0dTW output pixels, one per thread, plus a one-pixel halo; W0 staged in LDS.  Each dX element is written by one lane, taps
+// and channels summed in a fixed order: no atomics, bit-reproducible.  Out-of-image halo pixels hold 0 (the zero padding).
+constexpr int kC0dTH = 8, kC0dTW = 32, kC0dC = 24;
+constexpr int kC0dHW = kC0dTW + 2, kC0dNP = (kC0dTH + 2) * kC0dHW;   // 340 halo pixels
+constexpr int kC0dLd = 28;   // LDS floats per pixel: 112-byte rows put 16 consecutive lanes' ds_read_b128 on distinct banks
+constexpr int kC0dPP = 256 / (kC0dC / 4);                            // 42 halo pixels per staging pass (6 lanes each)
+constexpr int kC0dPasses = (kC0dNP + kC0dPP - 1) / kC0dPP;            // 9
+
+template <bool FUSED>
+__global__ __launch_bounds__(256) void conv0_bwd_data_kernel(
+    const float* __restrict__ Gd, int ldg, const float* __restrict__ X1, int ldx, const float* __restrict__ Y0,
+    const float* __restrict__ scale0, const float* __restrict__ shift0, const float* __restrict__ sB,
+    const float* __restrict__ sC, const float* __restrict__ cA, const float* __restrict__ cB, const float* __restrict__ cC,
+    const float* __restrict__ W0, int B, int H, int W, float* __restrict__ dX) {
+  __shared__ __attribute__((aligned(16))) float dz[kC0dNP * kC0dLd];
+  // W0 as [tap][c][o]: one broadcast ds_read_b128 gives four channels' weights (scalar loads of all 648 spill SGPRs)
+  __shared__ __attribute__((aligned(16))) float wl[9 * 3 * kC0dC];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < kC0dC * 27; e += 256) wl[((e % 9) * 3 + (e % 27) / 9) * kC0dC + e / 27] = W0[e];
+  // staging role: channel quad q of halo pixels s, s + 42, ... (lanes 252..255 idle)
+  const int q = tid % (kC0dC / 4), s0 = tid / (kC0dC / 4);
+  const bool stager = s0 < kC0dPP;
+  const int o4 = 4 * q;
+  const float4 ca = *reinterpret_cast<const float4*>(cA + o4), cb = *reinterpret_cast<const float4*>(cB + o4),
+               cc = *reinterpret_cast<const float4*>(cC + o4);
+  float4 fs0 = {0.f, 0.f, 0.f, 0.f}, ft0 = fs0, fb = fs0, fc = fs0;
+  if constexpr (FUSED) {
+    fs0 = *reinterpret_cast<const float4*>(scale0 + o4);
+    ft0 = *reinterpret_cast<const float4*>(shift0 + o4);
+    fb = *reinterpret_cast<const float4*>(sB + o4);
+    fc = *reinterpret_cast<const float4*>(sC + o4);
+  }
+  const float cav[4] = {ca.x, ca.y, ca.z, ca.w}, cbv[4] = {cb.x, cb.y, cb.z, cb.w}, ccv[4] = {cc.x, cc.y, cc.z, cc.w};
+  const float fsv[4] = {fs0.x, fs0.y, fs0.z, fs0.w}, ftv[4] = {ft0.x, ft0.y, ft0.z, ft0.w};
+  const float fbv[4] = {fb.x, fb.y, fb.z, fb.w}, fcv[4] = {fc.x, fc.y, fc.z, fc.w};
+  const int ty = tid / kC0dTW, tx = tid % kC0dTW;
+  // one tile per workgroup: a loop over tiles would make the 648 scalar weight loads loop-invariant and hoist them (SGPR spills)
+  const int tiles_x = (W + kC0dTW - 1) / kC0dTW, tiles_y = (H + kC0dTH - 1) / kC0dTH;
+  const size_t plane = (size_t)H * W;
+  {
+    const int b = (int)(blockIdx.x / (tiles_y * tiles_x));
+    const int r = (int)(blockIdx.x - b * tiles_y * tiles_x);
+    const int h0 = (r / tiles_x) * kC0dTH, w0 = (r % tiles_x) * kC0dTW;
+    // ---- stage dY0 of the halo: every load of the tile issued before the first is used
+    float4 gv[kC0dPasses], yv[kC0dPasses], xv[kC0dPasses];
+    bool in[kC0dPasses];
+#pragma unroll
+    for (int k = 0; k < kC0dPasses; ++k) {
+      const int s = s0 + k * kC0dPP;
+      const int hy = h0 - 1 + s / kC0dHW, hx = w0 - 1 + s % kC0dHW;
+      in[k] = stager && s < kC0dNP && hy >= 0 && hy < H && hx >= 0 && hx < W;
+      const size_t p = (size_t)b * plane + (size_t)(in[k] ? hy : 0) * W + (in[k] ? hx : 0);
+      gv[k] = in[k] ? *reinterpret_cast<const float4*>(Gd + p * ldg + o4) : float4{0.f, 0.f, 0.f, 0.f};
+      yv[k] = in[k] ? *reinterpret_cast<const float4*>(Y0 + p * kC0dC + o4) : float4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (!FUSED) xv[k] = in[k] ? *reinterpret_cast<const float4*>(X1 + p * ldx + o4) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < kC0dPasses; ++k) {
+      const int s = s0 + k * kC0dPP;
+      if (!stager || s >= kC0dNP) continue;
+      const float g4[4] = {gv[k].x, gv[k].y, gv[k].z, gv[k].w}, y4[4] = {yv[k].x, yv[k].y, yv[k].z, yv[k].w};
+      float d[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float g;
+        if constexpr (FUSED) {
+          const float xx = fmaxf(fmaf(y4[e], fsv[e], ftv[e]), 0.f);             // bn_apply's expression
+          g = xx > 0.f ? g4[e] + fmaf(fbv[e], xx, fcv[e]) : 0.f;               // grad_materialize's expression
+        } else {
+          const float x4[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+          g = x4[e] > 0.f ? g4[e] : 0.f;
+        }
+        d[e] = in[k] ? fmaf(cav[e], g, fmaf(cbv[e], y4[e], ccv[e])) : 0.f;  // conv0_bwd_weight_kernel's dY0
+      }
+      *reinterpret_cast<float4*>(&dz[s * kC0dLd + o4]) = float4{d[0], d[1], d[2], d[3]};
+    }
+    __syncthreads();
+    // ---- transposed 3x3: output pixel (h0 + ty, w0 + tx) reads halo pixels (ty + 2 - ky, tx + 2 - kx)
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const float* src = &dz[((ty + 2 - ky) * kC0dHW + (tx + 2 - kx)) * kC0dLd];
+        const float* wt = &wl[(ky * 3 + kx) * 3 * kC0dC];
+#pragma unroll
+        for (int o4i = 0; o4i < kC0dC / 4; ++o4i) {
+          const float4 v = *reinterpret_cast<const float4*>(src + 4 * o4i);
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float4 wq = *reinterpret_cast<const float4*>(wt + c * kC0dC + 4 * o4i);
+            const float ww[4] = {wq.x, wq.y, wq.z, wq.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[c] = fmaf(ww[e], vv[e], acc[c]);
+          }
+        }
+      }
+    const int h = h0 + ty, w = w0 + tx;
+    if (h < H && w < W) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dX[((size_t)b * 3 + c) * plane + (size_t)h * W + w] = acc[c];
+    }
+  }
+}
+
 // =============================================================================== head backward
 // dF[p][c] = (F[p][c] > 0) ? gpooled[b][c][oy/k][ox/k] / k^2 : 0
 __global__ __launch_bounds__(256) void head_pool_bwd_kernel(const float* __restrict__ gp, const float* __restrict__ F,
@@ -3395,4 +3505,29 @@ extern "C" int eml_dense_conv0_bwd_weight_fused_f32(const float* x, const float*
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(27 * 32 / 64 + 1), dim3(256), 0, (hipStream_t)stream, partial, grid * 4,
                      (size_t)1024, 2, 0, C0, 0, dW0);
   return eml::check_launch("eml_dense_conv0_bwd_weight_fused_f32(reduce)");
+}
+
+extern "C" int eml_dense_conv0_bwd_data_f32(const float* G, int ldg, const float* X1, int ldx, const float* Y0, int C0,
+                                            const float* scale0, const float* shift0, const float* sB, const float* sC,
+                                            const float* cA, const float* cB, const float* cC, const float* W0, int B, int H,
+                                            int W, float* dX, eml_stream_t stream) {
+  auto a16 = [](const void* q) { return (reinterpret_cast<size_t>(q) & 15) == 0; };
+  const bool fused = X1 == nullptr;
+  if (!G || !Y0 || !cA || !cB || !cC || !W0 || !dX || (fused && (!scale0 || !shift0 || !sB || !sC)))
+    return eml::fail(EML_EINVAL, "eml_dense_conv0_bwd_data_f32: null pointer");
+  if (C0 != kC0dC || B < 1 || H < 1 || W < 1 || ldg < C0 || (ldg & 3) || (!fused && (ldx < C0 || (ldx & 3))))
+    return eml::fail(EML_EINVAL, "eml_dense_conv0_bwd_data_f32: bad shape (C0 == 24, B, H, W >= 1, ldg / ldx >= 24 and multiples of 4)");
+  if (!a16(G) || !a16(Y0) || (!fused && !a16(X1)) || !a16(cA) || !a16(cB) || !a16(cC) ||
+      (fused && (!a16(scale0) || !a16(shift0) || !a16(sB) || !a16(sC))))
+    return eml::fail(EML_EINVAL, "eml_dense_conv0_bwd_data_f32: G, X1, Y0 and the coefficient vectors must be 16-byte aligned");
+  const size_t tiles = (size_t)B * ((H + kC0dTH - 1) / kC0dTH) * ((W + kC0dTW - 1) / kC0dTW);
+  if (tiles > 0x7fffffff) return eml::fail(EML_EINVAL, "eml_dense_conv0_bwd_data_f32: more than 2^31 - 1 tiles of 8 x 32 pixels");
+  const int grid = (int)tiles;
+  if (fused)
+    hipLaunchKernelGGL(conv0_bwd_data_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, G, ldg, nullptr, 0, Y0,
+                       scale0, shift0, sB, sC, cA, cB, cC, W0, B, H, W, dX);
+  else
+    hipLaunchKernelGGL(conv0_bwd_data_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, G, ldg, X1, ldx, Y0,
+                       nullptr, nullptr, nullptr, nullptr, cA, cB, cC, W0, B, H, W, dX);
+  return eml::check_launch("eml_dense_conv0_bwd_data_f32");
 }

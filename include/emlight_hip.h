@@ -453,6 +453,20 @@ int eml_dense_conv0_bwd_weight_fused_f32(const float* x, const float* G, int ldg
                                          const float* cA, const float* cB, const float* cC, int B, int H, int W,
                                          float* partial, float* dW0, int grid, eml_stream_t stream);
 
+/* conv0's data gradient: the input image's gradient of the encoder, DenseNet.py:88-93 under autograd (the transposed 3x3
+ * pad-1 convolution 24 -> 3).  An addition within ABI 31 (no existing signature changed; a library without it fails the
+ * binding's symbol check).  dX (B,3,H,W) NCHW, every element written:
+ *   dX[b][c][h][w] = sum_{o, ky, kx} W0[o][c][ky][kx] * dY0[b][h+1-ky][w+1-kx][o],
+ * dY0 = cA*g + cB*Y0 + cC rebuilt per pixel, never stored, with the expression conv0's weight gradient uses on the same path:
+ * X1 == NULL selects the fused form of eml_dense_conv0_bwd_weight_fused_f32 (x1 = relu(scale0*Y0 + shift0),
+ * g = x1 > 0 ? G + (sB*x1 + sC) : 0), otherwise that of eml_dense_conv0_bwd_weight_f32 (g = X1 > 0 ? G : 0; scale0, shift0,
+ * sB, sC unused).  C0 == 24; ldg, ldx multiples of 4; G, X1, Y0 and the coefficient vectors 16-byte aligned; W0 (C0,3,3,3).
+ * 64-bit offsets.  Each element is summed by one lane in a fixed order: bit-reproducible. */
+int eml_dense_conv0_bwd_data_f32(const float* G, int ldg, const float* X1, int ldx, const float* Y0, int C0,
+                                 const float* scale0, const float* shift0, const float* sB, const float* sC,
+                                 const float* cA, const float* cB, const float* cC, const float* W0, int B, int H, int W,
+                                 float* dX, eml_stream_t stream);
+
 /* dF = relu-mask(F) * unpool_k(gpooled) / k^2 : backward of DenseNet.py:136-137. */
 int eml_dense_head_pool_bwd_f32(const float* gpooled, const float* F, int ldf, int C, int B, int H,
                                 int W, int k, float* dF, int ldd, eml_stream_t stream);
