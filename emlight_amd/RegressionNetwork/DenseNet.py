@@ -16,7 +16,7 @@ containers (they give the reference's ``state_dict`` keys); they have no stock-o
 The same graph on stock PyTorch ops lives in ``oracle/densenet.py`` (test infrastructure).
 
 Supported configuration of the HIP engine: ``growth_rate=12``, ``bn_size=4`` (EMLight's
-constructor defaults), ``drop_rate=0``, any ``block_config`` whose widest block has at most 368
+constructor defaults), any ``drop_rate`` in [0, 1], any ``block_config`` whose widest block has at most 368
 channels (3 x 16 layers: 216 / 300 / 342); backward needs train-mode BatchNorm (EMLight trains
 and tests in train mode).  Anything else raises in the constructor or at the first call.
 
@@ -24,11 +24,24 @@ Differentiable, like the reference's stock-op module, in the input image and in 
 in any combination: ``x.requires_grad`` alone (frozen weights: a lighting-consistency loss,
 test-time optimisation of the input, saliency) gives ``x.grad``; frozen parameters get no
 ``.grad``.  One backward per forward (no ``retain_graph``, no double backward).
+
+Dropout (``drop_rate > 0``, ``DenseNet.py:50-55``): each dense layer drops its 12 new channels before the concatenation
+while that layer's ``training`` flag is set, reading its ``drop_rate`` at every forward.  The mask is a counter-based hash
+(Philox-4x32-10) of a 64-bit key, the layer, the pixel and the channel, applied inside the conv3x3 kernels and recomputed by
+the backward.  One key per forward is drawn from torch's default CPU generator, so ``torch.manual_seed`` reproduces a run;
+``set_dropout_key(key)`` pins it instead.  The masks are not bit-compatible with ``F.dropout``'s stream.
 """
 import math
 from collections import OrderedDict
 
 import torch.nn as nn
+
+
+def check_drop_rate(p):
+    """``F.dropout``'s rule: a probability in [0, 1]."""
+    if not (0 <= p <= 1):
+        raise ValueError("dropout probability has to be between 0 and 1, but got %r" % (p,))
+    return float(p)
 
 
 class _DenseLayer(nn.Module):
@@ -42,6 +55,7 @@ class _DenseLayer(nn.Module):
         self.norm2 = nn.BatchNorm2d(inter)
         self.conv2 = nn.Conv2d(inter, growth_rate, kernel_size=3, padding=1, bias=False)
         self.drop_rate = drop_rate
+        check_drop_rate(drop_rate)
 
     def forward(self, x):
         raise NotImplementedError("parameter container: the layer runs inside the HIP engine (DenseNet.pooled_features)")
@@ -101,11 +115,20 @@ class DenseNet(nn.Module):
         self.fc_intensity = nn.Linear(1024, 1)
         self.fc_rgb_ratio = nn.Linear(1024, 3)
         self.fc_ambient = nn.Linear(1024, 3)
-        if drop_rate > 0:
-            raise NotImplementedError("drop_rate > 0 is not on EMLight's path (reference default 0)")
+        check_drop_rate(drop_rate)
         from .dense_engine import HipDenseEncoder
         HipDenseEncoder.check_supported(self)   # reject configurations the kernels are not built for, up front
         self._hip = None
+        self.dropout_key = None
+
+    def set_dropout_key(self, key):
+        """Pin the 64-bit key of the dense layers' dropout masks (an int in [0, 2**64)): every later train-mode forward then
+        drops the same elements.  ``None`` (default): a fresh key per forward from torch's default CPU generator."""
+        if key is not None:
+            key = int(key)
+            if not 0 <= key < 2 ** 64:
+                raise ValueError("dropout key must be in [0, 2**64)")
+        self.dropout_key = key
 
     def pooled_features(self, x):
         """relu(last_norm3(...)) average-pooled and flattened: ``(B, fc.in_features)``."""

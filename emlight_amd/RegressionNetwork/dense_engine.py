@@ -26,6 +26,11 @@ def _r16(v):
     return (v + 15) // 16 * 16
 
 
+def _capturing(x):
+    """True while x's device stream is being captured into a graph."""
+    return x.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
 def _row_floats(ctot):
     """Row length of a block buffer: whole 128-byte lines (32 floats), so that every pixel row starts on a line.  The
     1x1 kernels read the prefix [0, k) of every row and HBM serves whole lines (FETCH_SIZE per layer,
@@ -216,6 +221,7 @@ class HipDenseEncoder:
         self.chunks_max = max((c + 47) // 48 for c in self.trans_cout)
         self._ws = {}
         self._cu = None
+        self.last_dropout_key = None   # the dropout key of the latest forward (None: no layer dropped)
 
     # ------------------------------------------------------------------ parameter plumbing
     def param_list(self):
@@ -336,13 +342,44 @@ class HipDenseEncoder:
                                               p(istd), *args, C, Cpad, eps, mom, int(training), p(scale), p(shift),
                                               st), "eml_dense_bn_prepare_f32")
 
+    def dropout_plan(self, x):
+        """(key, [[p of every dense layer of block b, 0.0 where it does not drop]]) of this forward, or (None, None) when no
+        layer drops.  DenseNet.py:50-55: ``F.dropout(new_features, p=self.drop_rate, training=self.training)`` -- each layer's
+        own flag and rate, read at every forward.  One 64-bit key per forward, drawn from torch's default CPU generator (no
+        launch, no host sync; ``torch.manual_seed`` reproduces it) unless the model pins one (``DenseNet.set_dropout_key``)."""
+        from .DenseNet import check_drop_rate
+        f = self.model.features
+        plan, any_drop = [], False
+        for bi, nl in enumerate(self.block_layers):
+            mod = getattr(f, "denseblock%d" % (bi + 1))
+            row = []
+            for l in range(nl):
+                Lm = getattr(mod, "denselayer%d" % (l + 1))
+                q = check_drop_rate(Lm.drop_rate)
+                row.append(q if (Lm.training and q > 0) else 0.0)
+                any_drop = any_drop or row[-1] > 0
+            plan.append(row)
+        if not any_drop:
+            return None, None
+        if _capturing(x):
+            raise RuntimeError("HIP DenseNet: drop_rate > 0 while the stream is being captured -- a captured graph would replay "
+                               "one fixed dropout mask on every replay; capture with drop_rate = 0 or in eval mode")
+        key = self.model.dropout_key
+        if key is None:
+            lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+            key = lo | (hi << 32)
+        return key, plan
+
     def run_forward(self, x, keep_all):
         L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
         m = self.model
         f = m.features
         B, _, H, W = x.shape
         dev = x.device
+        drop_key, drop_plan = self.dropout_plan(x)
         ws = self.workspace(B, H, W, dev, keep_all)
+        ws.drop_key, ws.drop_plan = drop_key, drop_plan   # the backward recomputes the masks from them
+        self.last_dropout_key = drop_key
         G = self._grid(dev)
         G3 = self._grid3(dev)
         Gf = self._tuned("EML_GRID_FWD1", G)   # per-family knob for A/B runs (default: the common 2 x #CU)
@@ -383,6 +420,7 @@ class HipDenseEncoder:
         nb = len(ws.blocks)
         for bi, blk in enumerate(ws.blocks):
             mod = getattr(f, "denseblock%d" % (bi + 1))
+            gl0 = sum(self.block_layers[:bi])   # global index of the block's first dense layer (the masks' counter)
             P, Hb, Wb, ld = blk["P"], blk["H"], blk["W"], blk["ld"]
             pending = False  # partial stats of the previous layer's 12 new channels wait in `part`
             Gc = G3          # ... in that many rows (the grid of the conv3x3 kernel that wrote them)
@@ -398,16 +436,18 @@ class HipDenseEncoder:
                            "eml_dense_conv1x1_fwd_f32")
                 self._prepare(L, st, part, Gf, 96, 48, 0, P, lay["zmean"], lay["zvar"], lay["zistd"], Lm.norm2, 48, 48,
                               training, lay["scale2"], lay["shift2"])
+                q = drop_plan[bi][l] if drop_plan is not None else 0.0
+                drop = (drop_key, gl0 + l, q) if q > 0 else ()   # DenseNet.py:50-55, inside the conv3x3 epilogue
                 if blk["tp"] is None or not training:
                     Gc = G3
-                    _lib.check(L.eml_dense_conv3x3_fwd_f32(p(z), p(lay["scale2"]), p(lay["shift2"]), p(lay["W2p"]),
-                                                           p(blk["X"]), ld, cin, B, Hb, Wb, p(part), G3, st),
-                               "eml_dense_conv3x3_fwd_f32")
+                    fn = "eml_dense_conv3x3_fwd_drop_f32" if drop else "eml_dense_conv3x3_fwd_f32"
+                    _lib.check(getattr(L, fn)(p(z), p(lay["scale2"]), p(lay["shift2"]), p(lay["W2p"]), p(blk["X"]), ld, cin,
+                                              B, Hb, Wb, p(part), G3, *drop, st), fn)
                 else:
                     band, Gc = blk["tp"]
-                    _lib.check(L.eml_dense_conv3x3_fwd_tp_f32(p(z), p(lay["scale2"]), p(lay["shift2"]), p(lay["W2t"]),
-                                                              p(blk["X"]), ld, cin, B, Hb, Wb, band, p(part), Gc, st),
-                               "eml_dense_conv3x3_fwd_tp_f32")
+                    fn = "eml_dense_conv3x3_fwd_tp_drop_f32" if drop else "eml_dense_conv3x3_fwd_tp_f32"
+                    _lib.check(getattr(L, fn)(p(z), p(lay["scale2"]), p(lay["shift2"]), p(lay["W2t"]), p(blk["X"]), ld, cin,
+                                              B, Hb, Wb, band, p(part), Gc, *drop, st), fn)
                 pending = True
             # ---- transition (BN-ReLU-1x1-avgpool2, DenseNet.py:14-21) + last_norm (DenseNet.py:122)
             tr, T = blk["trans"], getattr(f, "transition%d" % (bi + 1))

@@ -229,6 +229,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
         cout, Ko, kpt = tr["Cout"], tr["Ko"], tr["Kp"]
         Pn = B * (Hb // 2) * (Wb // 2)
         Gbuf = bw.G[bi]
+        gl0 = sum(enc.block_layers[:bi])   # global index of the block's first dense layer (the dropout masks' counter)
         top2 = bw.TOP[:2 * P * 12].view(2, P, 12) if bw.TOP is not None else None
         # ---- last_norm backward (affine folded into the transition kernels' dz operand)
         _lib.check(L.eml_dense_bn_bwd_stats_f32(p(dY), ld_dy, p(tr["T"]), Ko, None, 0, 0, cout, Pn, p(tr["tmean"]),
@@ -271,17 +272,19 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
             # blocks 1 and 2, pairs of 8-byte ones in block 3, which starts at channel 150) -- EML_C3_FOLD=0: the two launches (A/B)
             fold = (bw.side is None and c3_fold
                     and L.eml_dense_conv3x3_bwd_fused_supported(gsrc[1], gsrc[2], ld, cin) == 1)
+            # the layer's dropout (DenseNet.py:50-55): the staged g is multiplied by the forward's mask / (1 - p), recomputed
+            # from its key; GF12 -- what a separate weight gradient reads -- then holds the masked g as well
+            q = ws.drop_plan[bi][l] if ws.drop_plan is not None else 0.0
+            drop = (ws.drop_key, gl0 + l, q) if q > 0 else ()
             if fold:
-                _lib.check(L.eml_dense_conv3x3_bwd_fused_f32(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]), p(lay["zistd"]),
-                                                             p(dz), B, Hb, Wb, p(part), G3d, p(blk["X"]), ld, cin, p(sB),
-                                                             p(sC), p(bw.GF12[r]), p(lay["scale2"]), p(lay["shift2"]),
-                                                             p(bw.partW), gr(Lm.conv2.weight), st),
-                           "eml_dense_conv3x3_bwd_fused_f32")
+                fn = "eml_dense_conv3x3_bwd_fused_drop_f32" if drop else "eml_dense_conv3x3_bwd_fused_f32"
+                _lib.check(getattr(L, fn)(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]), p(lay["zistd"]), p(dz), B, Hb, Wb,
+                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.GF12[r]), p(lay["scale2"]),
+                                          p(lay["shift2"]), p(bw.partW), gr(Lm.conv2.weight), *drop, st), fn)
             else:
-                _lib.check(L.eml_dense_conv3x3_bwd_data_f32(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]),
-                                                            p(lay["zistd"]), p(dz), B, Hb, Wb, p(part), G3d, p(blk["X"]), ld,
-                                                            cin, p(sB), p(sC), p(bw.GF12[r]), st),
-                           "eml_dense_conv3x3_bwd_data_f32")
+                fn = "eml_dense_conv3x3_bwd_data_drop_f32" if drop else "eml_dense_conv3x3_bwd_data_f32"
+                _lib.check(getattr(L, fn)(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]), p(lay["zistd"]), p(dz), B, Hb, Wb,
+                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.GF12[r]), *drop, st), fn)
             if fold:
                 pass
             elif bw.side is None:

@@ -63,19 +63,21 @@ class RegressionTrainer:
 
     def __init__(self, anchors=96, crop_hw=(192, 256), blur=.025, diameter=None, lr=1e-4,
                  betas=(0.9, 0.999), device="cuda", world=1, bucket_cap_mb=64, model=None, sam_loss=None,
-                 sync_diameter=None, reach=None):
+                 sync_diameter=None, reach=None, drop_rate=0):
         """``model`` / ``sam_loss``: pre-built modules to train instead of the HIP ``DenseNet`` / ``SamplesLoss``
         (the CPU-only distributed tests inject the oracle's stock-op restatements; the product never does).
         ``sync_diameter``: derive the Sinkhorn eps-schedule from the range of the GLOBAL batch (2-float all-reduce per
         step) so that N ranks x B reproduce the single-process run with N*B samples (sinkhorn_divergence.py:9-18);
         default: on when world > 1 and no fixed ``diameter`` is given.
-        ``reach``: unbalanced OT in the Sinkhorn criterion (``SamplesLoss(reach=...)``); None (default): balanced."""
+        ``reach``: unbalanced OT in the Sinkhorn criterion (``SamplesLoss(reach=...)``); None (default): balanced.
+        ``drop_rate``: the encoder's dropout (``DenseNet(drop_rate=...)``, DenseNet.py:50-55); 0 (default): none."""
         from .._dist import dp_wrap, own_buckets, GradientBuckets
         if sync_diameter is None:
             sync_diameter = dp_wrap(world) and diameter is None
         self.ln = anchors
         self.device = torch.device(device)
-        self.model = (DenseNet(anchors=anchors, crop_hw=crop_hw) if model is None else model).to(self.device)
+        self.model = (DenseNet(anchors=anchors, crop_hw=crop_hw, drop_rate=drop_rate) if model is None
+                      else model).to(self.device)
         self.model.train()
         self.sam_loss = sam_loss or SamplesLoss("sinkhorn", p=2, blur=blur, reach=reach, diameter=diameter,
                                                 anchors=anchors, sync_diameter=sync_diameter)

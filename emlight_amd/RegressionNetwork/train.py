@@ -49,6 +49,8 @@ def main(argv=None):
     ap.add_argument("--diameter", type=float, default=None)
     ap.add_argument("--reach", type=float, default=None,
                     help="unbalanced OT in the Sinkhorn loss: SamplesLoss(reach=...); default: balanced")
+    ap.add_argument("--drop_rate", type=float, default=0,
+                    help="dropout of the dense layers' new channels: DenseNet(drop_rate=...); default: none")
     ap.add_argument("--sync_diameter", type=int, choices=(0, 1), default=None,
                     help="Sinkhorn eps-schedule from the range of the GLOBAL batch (2-float all-reduce per step); default: "
                          "on under torchrun unless --diameter is given (a single-process run sees the whole batch)")
@@ -62,7 +64,7 @@ def main(argv=None):
     rank, local, world = init_distributed()
     device = "cuda:%d" % local
     tr = RegressionTrainer(anchors=args.anchors, crop_hw=tuple(args.crop_hw), blur=args.blur,
-                           diameter=args.diameter, reach=args.reach, device=device, world=world,
+                           diameter=args.diameter, reach=args.reach, drop_rate=args.drop_rate, device=device, world=world,
                            sync_diameter=None if args.sync_diameter is None else bool(args.sync_diameter))
     if args.load:
         tr.model.load_state_dict(torch.load(args.load, map_location=device))

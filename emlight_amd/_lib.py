@@ -15,6 +15,7 @@ _i32p = ctypes.c_void_p
 _f64p = ctypes.c_void_p
 _stream = ctypes.c_void_p
 _int = ctypes.c_int
+_u64 = ctypes.c_ulonglong
 
 ABI_VERSION = 31   # == EML_ABI_VERSION of include/emlight_hip.h
 
@@ -143,6 +144,12 @@ SIGNATURES = {
     "eml_dense_conv3x3_fwd_tp_supported": (_int, [_int, _int, _int]),
     "eml_dense_conv3x3_fwd_tp_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _int, _int, _f32p,
                                             _int, _stream]),
+    # dropout of the dense layers' new channels (seed, global layer index, p)
+    "eml_dense_conv3x3_fwd_drop_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _int, _f32p,
+                                              _int, _u64, _int, ctypes.c_double, _stream]),
+    "eml_dense_conv3x3_fwd_tp_drop_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _int, _int, _f32p,
+                                                 _int, _u64, _int, ctypes.c_double, _stream]),
+    "eml_dense_dropout_mask_u16": (_int, [_u64, _int, ctypes.c_double, ctypes.c_long, ctypes.c_void_p, _stream]),
     "eml_dense_pool_act_f32": (_int, [_f32p, _int, _int, _int, _int, _int, _f32p, _f32p, _f32p, _int, ctypes.c_void_p,
                                       _stream]),
     "eml_dense_head_pool_fwd_f32": (_int, [_f32p, _int, _int, _int, _int, _int, _int, _f32p, _stream]),
@@ -152,6 +159,12 @@ SIGNATURES = {
     "eml_dense_conv3x3_bwd_fused_supported": (_int, [_int, _int, _int, _int]),
     "eml_dense_conv3x3_bwd_fused_f32": (_int, [_f32p, _int, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _f64p, _int,
                                                _f32p, _int, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _stream]),
+    "eml_dense_conv3x3_bwd_data_drop_f32": (_int, [_f32p, _int, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int,
+                                                   _f32p, _int, _f32p, _int, _int, _f32p, _f32p, _f32p, _u64, _int,
+                                                   ctypes.c_double, _stream]),
+    "eml_dense_conv3x3_bwd_fused_drop_f32": (_int, [_f32p, _int, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int,
+                                                    _f64p, _int, _f32p, _int, _int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                                    _f32p, _u64, _int, ctypes.c_double, _stream]),
     "eml_dense_conv3x3_bwd_weight_f32": (_int, [_f32p, _int, _int, _f32p, _f32p, _f32p, _int, _int, _int, _f32p,
                                                 _f32p, _int, _stream]),
     "eml_dense_bn_bwd_finalize_f32": (_int, [_f32p, _int, _int, ctypes.c_double, _f32p, _f32p, _f32p, _int, _int,

@@ -21,6 +21,7 @@
 // transition_bwd_data (un-pool, mask, accumulate), last_norm's backward folded into the dz affine.  All
 // reductions are per-block partials + a finishing kernel: deterministic, no atomics.
 #include "eml_common.h"
+#include "eml_dropout.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -68,12 +69,14 @@ constexpr int kGPass = kHH / kGRows;                        // 5 passes of float
 // workgroup per CU the two waves of a SIMD share a phase, so nobody issues MFMAs while both sit in the epilogue": measured
 // 15.34 against 14.43 ms per step -- SLOWER.  The kernel moves 4.0 TB/s with 43 % of its bytes written (dzn, GF): it sits on
 // what this part delivers for that read / write mix (4.0-4.7 TB/s, profiles/r03_row_access_probe.txt), not on its phases.
-template <bool FUSE, bool WIDE, int TH>
+// DROP (with FUSE): the staged g is multiplied by the layer's dropout mask / (1 - p) (eml_dropout.h), recomputed from the
+// forward's key at the halo pixel: the data gradient, its statistics and the compact GF all see the masked g.
+template <bool FUSE, bool WIDE, int TH, bool DROP = false>
 __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
     double* __restrict__ partials /*[grid][48][2]*/, const float* __restrict__ Xb, int ldx, int cx,
-    const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF) {
+    const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF, eml::DropKey dk) {
   constexpr int HH = TH + 2, NT = TH * 64;
   constexpr int GR = TH == 8 ? 2 : 1;                       // halo rows staged per pass of the float2 path
   constexpr int kNarrowPass = HH / GR;
@@ -132,6 +135,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
   const float* s_srcx = Xb;
   float* s_gf = GF;
   int s_y0 = 0;
+  unsigned s_pix0 = 0;     // (DROP, float2 path) flat pixel index of the staged column in image row 0
   bool s_col = false, s_own = false;
   int w_pix[kWP];          // clamped source pixel of the item (addresses are formed at the load: registers are scarce here)
   bool w_ok[kWP], w_own[kWP];
@@ -155,6 +159,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     s_y0 = ty * TH - 1 + s_row;
     s_col = gx >= 0 && gx < W;
     const size_t col = (size_t)b * H * W + min(max(gx, 0), W - 1);
+    if constexpr (DROP) s_pix0 = (unsigned)col;
     s_src = G + col * ldg + c0 + 2 * s_q;
     if constexpr (FUSE) {
       s_srcx = Xb + col * ldx + cx + 2 * s_q;
@@ -183,6 +188,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
         v.z = fmaf(fb4.z, xt4[it].z, v.z) + fc4.z;
         v.w = fmaf(fb4.w, xt4[it].w, v.w) + fc4.w;
       }
+      if constexpr (DROP) v = eml::drop4(dk, (unsigned)w_pix[it], (unsigned)w_q[it], v);   // channels 4 w_q .. + 3
       if (!w_ok[it]) v = make_float4(0.f, 0.f, 0.f, 0.f);
       float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
       *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
@@ -198,6 +204,11 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     if constexpr (FUSE) {
       v.x = ok ? fmaf(fb.x, xt[it].x, gt[it].x) + fc.x : 0.f;
       v.y = ok ? fmaf(fb.y, xt[it].y, gt[it].y) + fc.y : 0.f;
+      if constexpr (DROP) {   // channels 2 s_q, 2 s_q + 1: words 2 (s_q & 1), + 1 of Philox block s_q / 2
+        const uint4 d = eml::drop_draws(dk, s_pix0 + (unsigned)(min(max(gy, 0), H - 1) * W), (unsigned)(s_q >> 1));
+        v.x = eml::drop_apply(dk, (s_q & 1) ? d.z : d.x, v.x);
+        v.y = eml::drop_apply(dk, (s_q & 1) ? d.w : d.y, v.y);
+      }
     } else {
       v.x = ok ? gt[it].x : 0.f;
       v.y = ok ? gt[it].y : 0.f;
@@ -548,13 +559,15 @@ __device__ unsigned long long eml_c3_stamps[8];
 #endif
 // Needs the fused BN1 affine (X given).  A16: the 12-channel slices of G and X are 16-byte aligned (blocks 1 and 2); otherwise
 // (block 3 of EMLight's encoder starts at channel 150) each staged item is fetched as two 8-byte loads.
-template <bool A16>
+// DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
+template <bool A16, bool DROP = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
     double* __restrict__ partials /*[grid][48][2]*/, const float* __restrict__ Xb, int ldx, int cx,
     const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF,
-    const float* __restrict__ scale2, const float* __restrict__ shift2, float* __restrict__ partialW /*[2*grid][27][16][16]*/) {
+    const float* __restrict__ scale2, const float* __restrict__ shift2, float* __restrict__ partialW /*[2*grid][27][16][16]*/,
+    eml::DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kGT = kHH * kHW * kPSG;                 // floats of a g halo tile
   float* g_l = smem;                                    // [2][kGT]
@@ -645,6 +658,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
     v.y = fmaf(fb4.y, xt4[it].y, gt4[it].y) + fc4.y;
     v.z = fmaf(fb4.z, xt4[it].z, gt4[it].z) + fc4.z;
     v.w = fmaf(fb4.w, xt4[it].w, gt4[it].w) + fc4.w;
+    if constexpr (DROP) v = eml::drop4(dk, (unsigned)w_pix[it], (unsigned)w_q[it], v);
     if (!w_ok[it]) v = make_float4(0.f, 0.f, 0.f, 0.f);
     float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
     *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
@@ -859,13 +873,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
 // order): one partial row of 21 x 256 floats per workgroup (it was 2 x 27 x 256).  Data gradient, g staging and the phase
 // structure (A: data gradient, barrier, B: weight gradient with the data gradient's epilogue riding on it, barrier) are
 // conv3x3_bwd_fused_kernel's.
-template <bool A16>
+// DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
+template <bool A16, bool DROP = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
     double* __restrict__ partials /*[grid][48][2]*/, const float* __restrict__ Xb, int ldx, int cx,
     const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF,
-    const float* __restrict__ scale2, const float* __restrict__ shift2, float* __restrict__ partialW /*[grid][21][16][16]*/) {
+    const float* __restrict__ scale2, const float* __restrict__ shift2, float* __restrict__ partialW /*[grid][21][16][16]*/,
+    eml::DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kGT = kHH * kHW * kPSG;                 // floats of a g halo tile
   constexpr int kZS = 48;                               // pixel stride of the raw z tile (ds_read_b32 over 4 pixels x 16 channels)
@@ -977,6 +993,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     v.y = fmaf(fb4.y, xt4[it][1], gt4[it][1]) + fc4.y;
     v.z = fmaf(fb4.z, xt4[it][2], gt4[it][2]) + fc4.z;
     v.w = fmaf(fb4.w, xt4[it][3], gt4[it][3]) + fc4.w;
+    if constexpr (DROP) v = eml::drop4(dk, (unsigned)w_pix[it], (unsigned)w_q[it], v);
     if (!w_ok[it]) v = make_float4(0.f, 0.f, 0.f, 0.f);
     float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
     *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
@@ -3046,7 +3063,7 @@ extern "C" int eml_dense_conv3x3_bwd_data_f32(const float* G, int ldg, int c0, c
                     (!X || ((ldx & 3) == 0 && (cx & 3) == 0 && al16(X) && al16(sB) && al16(sC) && al16(GF)));
 #define EML_LAUNCH_D3(FUSEV, WIDEV, THV)                                                                                \
   hipLaunchKernelGGL((conv3x3_bwd_data_kernel<FUSEV, WIDEV, THV>), dim3(grid), dim3(THV * 64), 0, (hipStream_t)stream, G, ldg, \
-                     c0, W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF)
+                     c0, W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, eml::DropKey{})
   if (X) {
     if (tall) { if (wide) EML_LAUNCH_D3(true, true, 8); else EML_LAUNCH_D3(true, false, 8); }
     else      { EML_LAUNCH_D3(true, false, 4); }   // (the 16-byte staging spills 18 registers next to the fused affine here)
@@ -3056,6 +3073,38 @@ extern "C" int eml_dense_conv3x3_bwd_data_f32(const float* G, int ldg, int c0, c
   }
 #undef EML_LAUNCH_D3
   return eml::check_launch("eml_dense_conv3x3_bwd_data_f32");
+}
+
+extern "C" int eml_dense_conv3x3_bwd_data_drop_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                                   const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
+                                                   double* partials, int grid, const float* X, int ldx, int cx,
+                                                   const float* sB, const float* sC, float* GF, unsigned long long seed,
+                                                   int layer, double p, eml_stream_t stream) {
+  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || (c0 & 1) ||
+      (ldg & 1))
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: bad arguments");
+  if (!X || !sB || !sC || !GF || (ldx & 1))
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: fused affine needs X, sB, sC, GF");
+  if (cx < 0 || (cx & 1)) return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: cx must be even");
+  if (!(p >= 0.0 && p <= 1.0) || layer < 0)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", p,
+                     layer);
+  if ((long long)B * H * W > 0x7FFFFFFFll)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: B*H*W must fit the 32-bit pixel counter");
+  // the geometry choice of eml_dense_conv3x3_bwd_data_f32 (with X)
+  static const bool narrow = [] { const char* v = getenv("EML_D3_NARROW"); return v && v[0] == '1'; }();
+  static const bool tall = [] { const char* v = getenv("EML_D3_SHORT"); return !(v && v[0] == '1'); }();
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const bool wide = !narrow && (ldg & 3) == 0 && (c0 & 3) == 0 && al16(G) && (ldx & 3) == 0 && (cx & 3) == 0 && al16(X) &&
+                    al16(sB) && al16(sC) && al16(GF);
+  const eml::DropKey dk = eml_drop_key(seed, layer, p);
+#define EML_LAUNCH_D3(WIDEV, THV)                                                                                       \
+  hipLaunchKernelGGL((conv3x3_bwd_data_kernel<true, WIDEV, THV, true>), dim3(grid), dim3(THV * 64), 0, (hipStream_t)stream, G, \
+                     ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, dk)
+  if (tall) { if (wide) EML_LAUNCH_D3(true, 8); else EML_LAUNCH_D3(false, 8); }
+  else      { EML_LAUNCH_D3(false, 4); }
+#undef EML_LAUNCH_D3
+  return eml::check_launch("eml_dense_conv3x3_bwd_data_drop_f32");
 }
 
 extern "C" int eml_dense_conv3x3_bwd_weight_f32(const float* G, int ldg, int c0, const float* Z, const float* scale2,
@@ -3098,18 +3147,20 @@ extern "C" int eml_c3_read_stamps(unsigned long long* out, int reset) {
 extern "C" int eml_dense_conv3x3_bwd_fused_supported(int ldg, int c0, int ldx, int cx) {
   return ((ldg & 1) == 0 && (c0 & 1) == 0 && (ldx & 1) == 0 && (cx & 1) == 0) ? 1 : 0;
 }
-extern "C" int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
-                                               const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
-                                               double* partials, int grid, const float* X, int ldx, int cx,
-                                               const float* sB, const float* sC, float* GF, const float* scale2,
-                                               const float* shift2, float* partialW, float* dW2, eml_stream_t stream) {
+// one launch for the pair above (see conv3x3_bwd_fused_kernel); DROP: with the layer's dropout mask (dk)
+template <bool DROP>
+static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                    const float* zmean, const float* zistd, float* DZ, int B, int H, int W, double* partials,
+                                    int grid, const float* X, int ldx, int cx, const float* sB, const float* sC, float* GF,
+                                    const float* scale2, const float* shift2, float* partialW, float* dW2, eml::DropKey dk,
+                                    eml_stream_t stream) {
   if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || !X || !sB || !sC || !GF || !scale2 || !shift2 || !partialW ||
       !dW2 || B < 1 || H < 1 || W < 1 || grid < 1 || cx < 0)
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_fused_f32: bad arguments");
+    return eml::fail(EML_EINVAL, "%s: bad arguments", name);
   const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if (!eml_dense_conv3x3_bwd_fused_supported(ldg, c0, ldx, cx) || !al16(G) || !al16(X) || !al16(GF) || !al16(Z) || !al16(scale2) ||
       !al16(shift2))
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_fused_f32: needs even ldg, c0, ldx, cx and 16-byte aligned buffers");
+    return eml::fail(EML_EINVAL, "%s: needs even ldg, c0, ldx, cx and 16-byte aligned buffers", name);
   const bool a16 = (ldg & 3) == 0 && (c0 & 3) == 0 && (ldx & 3) == 0 && (cx & 3) == 0;
 #ifndef EML_C3_WTP   // experiment builds (tools/exp_build.sh nowtp -DEML_C3_WTP=0): round 4's weight gradient (27 tiles, z halo)
 #define EML_C3_WTP 1
@@ -3117,36 +3168,89 @@ extern "C" int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, 
 #if EML_C3_WTP
   const size_t lds = (size_t)(2 * kHH * kHW * kPSG + 2 * kTH * kTW * 48 + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);   // 163 392 of 163 840 bytes
   if (a16) {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true>), lds);
-    hipLaunchKernelGGL(conv3x3_bwd_fused_tp_kernel<true>, dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW);
+    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP>), lds);
+    hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
   } else {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false>), lds);
-    hipLaunchKernelGGL(conv3x3_bwd_fused_tp_kernel<false>, dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW);
+    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP>), lds);
+    hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
   }
-  int rc = eml::check_launch("eml_dense_conv3x3_bwd_fused_f32");
+  int rc = eml::check_launch(name);
   if (rc) return rc;
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(21 * 256 / 64), dim3(256), 0, (hipStream_t)stream, partialW, grid,
                      (size_t)21 * 256, 3, 0, 0, 0, dW2);
-  return eml::check_launch("eml_dense_conv3x3_bwd_fused_f32(reduce)");
+  return eml::check_launch(DROP ? "eml_dense_conv3x3_bwd_fused_drop_f32(reduce)" : "eml_dense_conv3x3_bwd_fused_f32(reduce)");
 #else
   const size_t lds = (size_t)(2 * kHH * kHW * kPSG + kHH * kHW * kPSW + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);
   if (a16) {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true>), lds);
-    hipLaunchKernelGGL(conv3x3_bwd_fused_kernel<true>, dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW);
+    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP>), lds);
+    hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
   } else {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false>), lds);
-    hipLaunchKernelGGL(conv3x3_bwd_fused_kernel<false>, dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW);
+    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP>), lds);
+    hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
   }
-  int rc = eml::check_launch("eml_dense_conv3x3_bwd_fused_f32");
+  int rc = eml::check_launch(name);
   if (rc) return rc;
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(27 * 256 / 64), dim3(256), 0, (hipStream_t)stream, partialW, 2 * grid,
                      (size_t)27 * 256, 1, 0, 0, 0, dW2);
-  return eml::check_launch("eml_dense_conv3x3_bwd_fused_f32(reduce)");
+  return eml::check_launch(DROP ? "eml_dense_conv3x3_bwd_fused_drop_f32(reduce)" : "eml_dense_conv3x3_bwd_fused_f32(reduce)");
 #endif
+}
+
+extern "C" int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                               const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
+                                               double* partials, int grid, const float* X, int ldx, int cx,
+                                               const float* sB, const float* sC, float* GF, const float* scale2,
+                                               const float* shift2, float* partialW, float* dW2, eml_stream_t stream) {
+  return conv3x3_bwd_fused_launch<false>("eml_dense_conv3x3_bwd_fused_f32", G, ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W, partials,
+                                         grid, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dW2, eml::DropKey{}, stream);
+}
+
+extern "C" int eml_dense_conv3x3_bwd_fused_drop_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                                    const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
+                                                    double* partials, int grid, const float* X, int ldx, int cx,
+                                                    const float* sB, const float* sC, float* GF, const float* scale2,
+                                                    const float* shift2, float* partialW, float* dW2, unsigned long long seed,
+                                                    int layer, double p, eml_stream_t stream) {
+  if (!(p >= 0.0 && p <= 1.0) || layer < 0)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_fused_drop_f32: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", p,
+                     layer);
+  if ((long long)B * H * W > 0x7FFFFFFFll)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_fused_drop_f32: B*H*W must fit the 32-bit pixel counter");
+  return conv3x3_bwd_fused_launch<true>("eml_dense_conv3x3_bwd_fused_drop_f32", G, ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W,
+                                        partials, grid, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dW2,
+                                        eml_drop_key(seed, layer, p), stream);
+}
+
+namespace {
+// the dropout mask of one dense layer: out[pixel] bit c (c < 12) = channel c kept (eml_dropout.h), for the tests
+__global__ __launch_bounds__(256) void dropout_mask_kernel(eml::DropKey dk, unsigned P, unsigned short* __restrict__ out) {
+  for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < P; q += gridDim.x * 256u) {
+    unsigned m = 0;
+#pragma unroll
+    for (unsigned grp = 0; grp < 3; ++grp) {
+      const uint4 d = eml::drop_draws(dk, q, grp);
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        if ((unsigned long long)eml::draw_word(d, w) >= dk.thr) m |= 1u << (4 * grp + w);
+    }
+    out[q] = (unsigned short)m;
+  }
+}
+}  // namespace
+
+extern "C" int eml_dense_dropout_mask_u16(unsigned long long seed, int layer, double p, long P, unsigned short* mask,
+                                          eml_stream_t stream) {
+  if (!mask || P < 1 || P > 0x7FFFFFFFl || layer < 0 || !(p >= 0.0 && p <= 1.0))
+    return eml::fail(EML_EINVAL, "eml_dense_dropout_mask_u16: bad arguments (mask null, P outside [1, 2^31), layer < 0 or p "
+                                 "outside [0, 1])");
+  const unsigned grid = (unsigned)std::min<long>((P + 255) / 256, 4096);
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eml_drop_key(seed, layer, p), (unsigned)P,
+                     mask);
+  return eml::check_launch("eml_dense_dropout_mask_u16");
 }
 
 extern "C" int eml_dense_bn_bwd_finalize_f32(const double* partials, int R, int pstride, double count,

@@ -22,6 +22,7 @@
 // Batch statistics for train-mode BN are emitted by every producer's epilogue as per-block
 //   f64 partial (sum, sumsq) and finished by bn_prepare -- deterministic, no atomics.
 #include "eml_common.h"
+#include "eml_dropout.h"
 
 namespace {
 
@@ -330,10 +331,12 @@ constexpr int kPS = 56;                     // LDS pixel stride: 56 dwords makes
 // alternated "all waves wait for HBM" / "all waves compute": 39 % of the f32 MFMA peak, 1.9 TB/s.)
 constexpr int kC3Threads = 512;
 
+// DROP: the layer's dropout (eml_dropout.h) is applied to the accumulators before the stores to X and the statistics
+template <bool DROP>
 __global__ __launch_bounds__(kC3Threads) void conv3x3_fwd_kernel(
     const float* __restrict__ Z, const float* __restrict__ scale2, const float* __restrict__ shift2,
     const float* __restrict__ W2p, float* __restrict__ X, int ldx, int c_out0, int B, int H, int W,
-    double* __restrict__ partials) {
+    double* __restrict__ partials, eml::DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* st_l = smem + 2 * kHH * kHW * kPS;               // [2][48]
   double* red = reinterpret_cast<double*>(st_l + 96);     // [8][16][2]
@@ -462,6 +465,11 @@ __global__ __launch_bounds__(kC3Threads) void conv3x3_fwd_kernel(
     for (int m = 0; m < 2; ++m) {
       const int gx = tx * kTW + 16 * m + r;
       const bool ok = gy < H && gx < W && kk < 3;  // channels 12..15 are MFMA padding
+      if constexpr (DROP) {   // channels 4kk .. 4kk + 3 of pixel (b, gy, gx): one Philox block
+        const float4 d = eml::drop4(dk, (unsigned)((b * H + gy) * W + gx), (unsigned)kk,
+                                    make_float4(acc[m][0], acc[m][1], acc[m][2], acc[m][3]));
+        acc[m] = f32x4{d.x, d.y, d.z, d.w};
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float v = ok ? acc[m][g] : 0.f;
@@ -1125,10 +1133,26 @@ extern "C" int eml_dense_conv3x3_fwd_f32(const float* Z, const float* scale2, co
   if (!Z || !scale2 || !shift2 || !W2p || !X || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || c_out0 + 12 > ldx || (c_out0 & 1) || (ldx & 1))
     return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_f32: bad arguments");
   const size_t lds = (size_t)(2 * kHH * kHW * kPS + 96) * sizeof(float) + 8 * 16 * 2 * sizeof(double);
-  EML_ENSURE_LDS((&conv3x3_fwd_kernel), lds);
-  hipLaunchKernelGGL(conv3x3_fwd_kernel, dim3(grid), dim3(kC3Threads), lds, (hipStream_t)stream, Z, scale2, shift2, W2p, X, ldx,
-                     c_out0, B, H, W, partials);
+  EML_ENSURE_LDS((&conv3x3_fwd_kernel<false>), lds);
+  hipLaunchKernelGGL(conv3x3_fwd_kernel<false>, dim3(grid), dim3(kC3Threads), lds, (hipStream_t)stream, Z, scale2, shift2, W2p, X,
+                     ldx, c_out0, B, H, W, partials, eml::DropKey{});
   return eml::check_launch("eml_dense_conv3x3_fwd_f32");
+}
+
+extern "C" int eml_dense_conv3x3_fwd_drop_f32(const float* Z, const float* scale2, const float* shift2, const float* W2p,
+                                              float* X, int ldx, int c_out0, int B, int H, int W, double* partials, int grid,
+                                              unsigned long long seed, int layer, double p, eml_stream_t stream) {
+  if (!Z || !scale2 || !shift2 || !W2p || !X || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || c_out0 + 12 > ldx || (c_out0 & 1) || (ldx & 1))
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_drop_f32: bad arguments");
+  if (!(p >= 0.0 && p <= 1.0) || layer < 0)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_drop_f32: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", p, layer);
+  if ((long long)B * H * W > 0x7FFFFFFFll)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_drop_f32: B*H*W must fit the 32-bit pixel counter");
+  const size_t lds = (size_t)(2 * kHH * kHW * kPS + 96) * sizeof(float) + 8 * 16 * 2 * sizeof(double);
+  EML_ENSURE_LDS((&conv3x3_fwd_kernel<true>), lds);
+  hipLaunchKernelGGL(conv3x3_fwd_kernel<true>, dim3(grid), dim3(kC3Threads), lds, (hipStream_t)stream, Z, scale2, shift2, W2p, X,
+                     ldx, c_out0, B, H, W, partials, eml_drop_key(seed, layer, p));
+  return eml::check_launch("eml_dense_conv3x3_fwd_drop_f32");
 }
 
 extern "C" int eml_dense_pool_act_f32(const float* X, int ldx, int B, int Hin, int Win, int Kp, const float* scale,

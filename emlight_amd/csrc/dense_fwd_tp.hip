@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "eml_common.h"
+#include "eml_dropout.h"
 
 namespace {
 
@@ -47,11 +48,12 @@ __device__ __forceinline__ float shl15(float v) { return eml::dpp_mov<0x10F>(v);
 // which row tiles a row is multiplied with
 enum { kFull = 0, kTop = 1 /* input row above the band: dy = -1 taps, tiles 0..2 */, kBot = 2 /* below: dy = +1, tiles 4..6 */ };
 
-template <int TX>
+// DROP: the layer's dropout (eml_dropout.h) is applied to a finished output row before its store and its statistics
+template <int TX, bool DROP>
 __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
     const float* __restrict__ Z, const float* __restrict__ scale2, const float* __restrict__ shift2,
     const float* __restrict__ W2t /* [7][3][64] float4 */, float* __restrict__ X, int ldx, int c_out0, int B, int H, int W,
-    int band, double* __restrict__ partials) {
+    int band, double* __restrict__ partials, eml::DropKey dk) {
   __shared__ float junk[64 + 36];
   __shared__ float edge[2][kNWMax][2][9][4];   // [row parity][wave][side][3 (dy + 1) + o][lane group]: written by the wave's edge lanes
   __shared__ double red[kNWMax][12][2];
@@ -247,9 +249,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
       const int yo = yi - 1;
       if (yo >= y0 && yo < y1) {
         float ls[3] = {0.f, 0.f, 0.f}, lq[3] = {0.f, 0.f, 0.f};
+        // dropout: bit 3 ti + o = channel 3kk + o of this lane's pixel in tile ti is kept.  Lane group kk needs words of the
+        // Philox blocks of channels 3kk / 4 and (3kk + 2) / 4, one block at a time in a rolled loop: every register of the
+        // row's windows is live here, and the TX hash chains side by side spilled 51 of them
+        unsigned keep = 0;
+        if constexpr (DROP) {
+          const int c0 = 3 * kk;
+#pragma unroll 1
+          for (int e = 0; e < 2 * TX; ++e) {
+            const int ti = e >> 1, grp = (c0 + 2 * (e & 1)) >> 2;
+            const uint4 d = eml::drop_draws(dk, (unsigned)((b * H + yo) * W + xcol + 16 * ti), (unsigned)grp);
+#pragma unroll
+            for (int o = 0; o < 3; ++o) {
+              const int c = c0 + o;
+              if ((c >> 2) == grp && (unsigned long long)eml::draw_word(d, c & 3) >= dk.thr) keep |= 1u << (3 * ti + o);
+            }
+          }
+        }
 #pragma unroll
         for (int ti = 0; ti < TX; ++ti) {
           float* dst = xb + ((size_t)yo * W + 16 * ti) * ldx;
+          if constexpr (DROP) {
+#pragma unroll
+            for (int o = 0; o < 3; ++o) wa[ti][o] = (keep >> (3 * ti + o)) & 1 ? wa[ti][o] * dk.scale : 0.f;
+          }
 #ifndef TP_NOSTORE   // experiment build: nothing written
           struct __attribute__((packed, aligned(4))) f3 { float a, b, c; };   // one global_store_dwordx3 (4-byte aligned)
           *reinterpret_cast<f3*>(dst) = f3{wa[ti][0], wa[ti][1], wa[ti][2]};
@@ -334,10 +357,36 @@ extern "C" int eml_dense_conv3x3_fwd_tp_f32(const float* Z, const float* scale2,
     return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_tp_f32: W = %d is not 16 * {4,5} * {1,2,4} (eml_dense_conv3x3_fwd_tp_supported)", W);
   // every one of the `grid` workgroups writes its partial row (zeros when it owns no band): bn_prepare folds `grid` rows
   if (tx == 5)
-    hipLaunchKernelGGL(conv3x3_fwd_tp_kernel<5>, dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t, X, ldx,
-                       c_out0, B, H, W, band_rows, partials);
+    hipLaunchKernelGGL((conv3x3_fwd_tp_kernel<5, false>), dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t,
+                       X, ldx, c_out0, B, H, W, band_rows, partials, eml::DropKey{});
   else
-    hipLaunchKernelGGL(conv3x3_fwd_tp_kernel<4>, dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t, X, ldx,
-                       c_out0, B, H, W, band_rows, partials);
+    hipLaunchKernelGGL((conv3x3_fwd_tp_kernel<4, false>), dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t,
+                       X, ldx, c_out0, B, H, W, band_rows, partials, eml::DropKey{});
   return eml::check_launch("eml_dense_conv3x3_fwd_tp_f32");
+}
+
+extern "C" int eml_dense_conv3x3_fwd_tp_drop_f32(const float* Z, const float* scale2, const float* shift2, const float* W2t,
+                                                 float* X, int ldx, int c_out0, int B, int H, int W, int band_rows,
+                                                 double* partials, int grid, unsigned long long seed, int layer, double p,
+                                                 eml_stream_t stream) {
+  if (!Z || !scale2 || !shift2 || !W2t || !X || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || band_rows < 1 ||
+      c_out0 + 12 > ldx || c_out0 < 0)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_tp_drop_f32: bad arguments");
+  if (!(p >= 0.0 && p <= 1.0) || layer < 0)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_tp_drop_f32: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", p,
+                     layer);
+  if ((long long)B * H * W > 0x7FFFFFFFll)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_tp_drop_f32: B*H*W must fit the 32-bit pixel counter");
+  int nw = 0;
+  const int tx = tp_tiles(W, &nw);
+  if (!tx)
+    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_fwd_tp_drop_f32: W = %d is not 16 * {4,5} * {1,2,4} (eml_dense_conv3x3_fwd_tp_supported)", W);
+  const eml::DropKey dk = eml_drop_key(seed, layer, p);
+  if (tx == 5)
+    hipLaunchKernelGGL((conv3x3_fwd_tp_kernel<5, true>), dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t,
+                       X, ldx, c_out0, B, H, W, band_rows, partials, dk);
+  else
+    hipLaunchKernelGGL((conv3x3_fwd_tp_kernel<4, true>), dim3(grid), dim3(64 * nw), 0, (hipStream_t)stream, Z, scale2, shift2, W2t,
+                       X, ldx, c_out0, B, H, W, band_rows, partials, dk);
+  return eml::check_launch("eml_dense_conv3x3_fwd_tp_drop_f32");
 }

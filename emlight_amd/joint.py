@@ -41,12 +41,15 @@ def predicted_gaussian_map(pred, ln, pano_hw=(128, 256)):
 
 class JointTrainer:
     def __init__(self, opt=None, anchors=128, crop_hw=(240, 320), blur=.05, diameter=None, device="cuda", world=1,
-                 pano_hw=(128, 256), encoder=None, sam_loss=None, sync_diameter=None, vgg_features=None, reach=None):
-        """``encoder`` / ``sam_loss`` / ``reach``: see ``RegressionTrainer`` (CPU-only distributed tests inject the oracle's);
+                 pano_hw=(128, 256), encoder=None, sam_loss=None, sync_diameter=None, vgg_features=None, reach=None,
+                 drop_rate=0):
+        """``encoder`` / ``sam_loss`` / ``reach`` / ``drop_rate``: see ``RegressionTrainer`` (CPU-only distributed tests
+        inject the oracle's);
         ``vgg_features``: see ``GenProjector.model_trainer.Trainer``."""
         self.ln, self.pano_hw, self.world = anchors, tuple(pano_hw), world
         self.reg = RegressionTrainer(anchors=anchors, crop_hw=crop_hw, blur=blur, diameter=diameter, device=device,
-                                     world=world, model=encoder, sam_loss=sam_loss, sync_diameter=sync_diameter, reach=reach)
+                                     world=world, model=encoder, sam_loss=sam_loss, sync_diameter=sync_diameter, reach=reach,
+                                     drop_rate=drop_rate)
         self.proj = Trainer(opt or networks.default_options(), device=device, world=world, vgg_features=vgg_features)
         self.losses = {}
 
@@ -120,6 +123,8 @@ def main(argv=None):
     ap.add_argument("--blur", type=float, default=.05)
     ap.add_argument("--reach", type=float, default=None,
                     help="unbalanced OT in the Sinkhorn loss: SamplesLoss(reach=...); default: balanced")
+    ap.add_argument("--drop_rate", type=float, default=0,
+                    help="dropout of the dense layers' new channels: DenseNet(drop_rate=...); default: none")
     ap.add_argument("--ngf", type=int, default=64)
     ap.add_argument("--ndf", type=int, default=64)
     ap.add_argument("--max_iters", type=int, default=100)
@@ -129,7 +134,8 @@ def main(argv=None):
     dev = "cuda:%d" % local
     tr = JointTrainer(networks.default_options(ngf=args.ngf, ndf=args.ndf, **networks.vgg_options(args, verbose=rank == 0)),
                       anchors=args.anchors,
-                      crop_hw=tuple(args.crop_hw), blur=args.blur, device=dev, world=world, reach=args.reach)
+                      crop_hw=tuple(args.crop_hw), blur=args.blur, device=dev, world=world, reach=args.reach,
+                      drop_rate=args.drop_rate)
     for it in range(args.max_iters):
         batch = joint_batch(args.batch, dev, args.anchors, tuple(args.crop_hw), seed=1234 + rank + 977 * it)
         losses = tr.step(batch)

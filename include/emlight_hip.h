@@ -257,6 +257,26 @@ int eml_dense_conv3x3_fwd_tp_f32(const float* Z, const float* scale2, const floa
                                  const float* W2t, float* X, int ldx, int c_out0, int B, int H, int W,
                                  int band_rows, double* partials, int grid, eml_stream_t stream);
 
+/* Dropout of the dense layer's 12 new channels, F.dropout(new_features, p, training) of DenseNet.py:50-55 (after conv2,
+ * before the concatenation), inside the two conv3x3 forwards above: the same arguments, plus the 64-bit key `seed`, the
+ * GLOBAL dense-layer index `layer` (0..47 in EMLight) and p in [0, 1].  Element (pixel q = (b*H + h)*W + w, channel c) is
+ * kept iff word c % 4 of Philox-4x32-10(counter (q, c / 4, layer, 0), key (seed & 0xffffffff, seed >> 32)) is
+ * >= floor(p * 2^32), and then scaled by 1/(1 - p); dropped elements are 0 in X, and the partial sums are taken over what is
+ * stored.  The mask depends on (seed, layer, q, c) only: the halo-tile and tap-packed kernels drop the same elements, and
+ * the backward launches below recompute them.  Not bit-compatible with torch's dropout stream.  p == 1: zeros, no inf
+ * scale.  B*H*W < 2^31.  Additions within ABI 31 (no existing signature changed; the binding refuses a library without
+ * them).  eml_dense_dropout_mask_u16: the mask of one layer, bit c of mask[q] (q < P) set iff channel c is kept. */
+int eml_dense_conv3x3_fwd_drop_f32(const float* Z, const float* scale2, const float* shift2,
+                                   const float* W2p, float* X, int ldx, int c_out0, int B, int H, int W,
+                                   double* partials, int grid, unsigned long long seed, int layer, double p,
+                                   eml_stream_t stream);
+int eml_dense_conv3x3_fwd_tp_drop_f32(const float* Z, const float* scale2, const float* shift2,
+                                      const float* W2t, float* X, int ldx, int c_out0, int B, int H, int W,
+                                      int band_rows, double* partials, int grid, unsigned long long seed, int layer,
+                                      double p, eml_stream_t stream);
+int eml_dense_dropout_mask_u16(unsigned long long seed, int layer, double p, long P, unsigned short* mask,
+                               eml_stream_t stream);
+
 /* Transition operand: A[p'][c] = 2x2 mean of relu(scale[c]*X + shift[c]), p' over (B, Hin/2, Win/2), c < Kp
  * (Kp % 4 == 0; padded channels have scale = shift = 0).  The transition's 1x1 conv and its weight gradient
  * run on A with pool = 0 and a unit BN (scale 1, shift 0) -- replaces torch's avg_pool2d after the conv in
@@ -305,6 +325,23 @@ int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float
                                     double* partials, int grid, const float* X, int ldx, int cx,
                                     const float* sB, const float* sC, float* GF, const float* scale2,
                                     const float* shift2, float* partialW, float* dW2, eml_stream_t stream);
+
+/* Backward of the dense layer's dropout (DenseNet.py:50-55 under autograd) inside the two conv3x3 backwards above (with the
+ * fused BN1 affine: X, sB, sC, GF required): the staged g = G + sB*x + sC is multiplied by mask/(1 - p), the mask recomputed
+ * from the forward's (seed, layer, p) -- see eml_dense_conv3x3_fwd_drop_f32.  dzn, its partial sums, the compact GF (what
+ * eml_dense_conv3x3_bwd_weight_f32 then reads) and the fused dW2 all use the masked g.  Otherwise the arguments of
+ * eml_dense_conv3x3_bwd_data_f32 / eml_dense_conv3x3_bwd_fused_f32.  Additions within ABI 31. */
+int eml_dense_conv3x3_bwd_data_drop_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                        const float* zmean, const float* zistd, float* DZ, int B, int H,
+                                        int W, double* partials, int grid, const float* X, int ldx, int cx,
+                                        const float* sB, const float* sC, float* GF, unsigned long long seed,
+                                        int layer, double p, eml_stream_t stream);
+int eml_dense_conv3x3_bwd_fused_drop_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                         const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
+                                         double* partials, int grid, const float* X, int ldx, int cx,
+                                         const float* sB, const float* sC, float* GF, const float* scale2,
+                                         const float* shift2, float* partialW, float* dW2, unsigned long long seed,
+                                         int layer, double p, eml_stream_t stream);
 
 /* dW2 (12,48,3,3) = sum_p G[p, c0:c0+12] (x) (scale2*Z + shift2)[p+tap]; partial: 2*grid*27*256 floats (two pixel halves per block). */
 int eml_dense_conv3x3_bwd_weight_f32(const float* G, int ldg, int c0, const float* Z,
