@@ -13,6 +13,12 @@ matrix is stored once, not ``batchsize`` times (``utils.py:80-81``).
 the loop by ``1 / (1 + eps / rho)`` (``:43-44, 78-107``; ``eml_sinkhorn_fwd_rho_f32``), and the loss is the fork's
 ``<alpha, b_x - a_x> + <beta, a_y - b_y>`` of the damped duals (``:65-69``, which ignores rho) -- not upstream geomloss's
 unbalanced divergence with its exponentially transformed dual terms.
+
+Samples may be D-dimensional, ``(B, N, D)`` with ``1 <= D <= MAX_DIM`` as in the reference (``utils.py:85-99``: the cost
+``.5 * (.1 * |x_i - y_j|^2 + M_ij)``; ``sinkhorn_divergence.py:9-18``: the diameter over the per-component ranges);
+``D = 1`` makes exactly the calls it always made, ``D > 1`` calls ``eml_sinkhorn_fwd_dim_f32``.  Weights passed in the
+four- or six-argument form get gradients when they require them: ``(b_x - a_x)`` and ``(a_y - b_y)`` of the final duals
+(``:65-69``; the weights enter the loop only through detached log-weights), ``eml_sinkhorn_bwd_weights_f32``.
 """
 import math
 
@@ -24,6 +30,7 @@ from ..util import sphere_points
 
 
 EML_SINKHORN_NO_SPLIT, EML_SINKHORN_FORCE_SPLIT, EML_SINKHORN_TEST_STALL = 1, 2, 4   # include/emlight_hip.h
+MAX_DIM = 8   # EML_SINKHORN_MAX_DIM: the largest point dimension D the kernels take
 
 
 def split_eligible(N):
@@ -109,9 +116,16 @@ def reach_to_rho(reach, p):
         return math.inf
 
 
-def sinkhorn_outputs(B, N, dev, need_gx=True, need_gy=False):
-    """Device buffers one ``eml_sinkhorn_fwd_ex_f32`` call writes (the caller owns every buffer, include/emlight_hip.h)."""
+def sinkhorn_outputs(B, N, dev, need_gx=True, need_gy=False, D=1):
+    """Device buffers one ``eml_sinkhorn_fwd_ex_f32`` call writes (the caller owns every buffer, include/emlight_hip.h).
+    ``D > 1``: the buffers of ``eml_sinkhorn_fwd_dim_f32`` -- gradients ``(B, N, D)``, its own scratch size."""
     f32 = dict(dtype=torch.float32, device=dev)
+    if D != 1:
+        work = torch.empty(max(int(_lib.lib().eml_sinkhorn_dim_work_floats(B, N, D)), (4 + 4 * D) * B * N), **f32)
+        return {"eps_s": torch.empty(64, **f32), "n_eps": torch.empty(1, dtype=torch.int32, device=dev),
+                "diameter": torch.empty(1, **f32), "loss": torch.empty(B, **f32),
+                "gx": torch.empty(B, N, D, **f32) if need_gx else None,
+                "gy": torch.empty(B, N, D, **f32) if need_gy else None, "work": work}
     n_work = max(int(_lib.lib().eml_sinkhorn_work_floats(B, N)), 8 * B * N)
     work = torch.empty(n_work, **f32)
     if split_eligible(N) and n_work > 24 * B * N:
@@ -128,12 +142,22 @@ def global_range(x, y):
     """(2,) tensor (min, max) of x U y over the batch of EVERY data-parallel rank, without a host sync: the local extrema,
     then ONE 2-float all-reduce (MIN over (min, -max)).  ``max_diameter`` (sinkhorn_divergence.py:9-18) takes the range
     over the whole batch, so a rank that only scanned its own shard would derive a different eps-schedule than the
-    single-process run with the global batch.  With one rank this is just the local range."""
+    single-process run with the global batch.  With one rank this is just the local range.
+    ``x, y`` of shape ``(B, N, D)``: the (2*D,) per-component minima then maxima (``max_diameter`` takes the norm of the
+    per-component ranges), all-reduced in the same one call."""
     import torch.distributed as dist
+    from ..._dist import dp_active
+    if x.dim() == 3:
+        D = x.shape[-1]
+        lo = torch.minimum(x.detach().reshape(-1, D).amin(0), y.detach().reshape(-1, D).amin(0))
+        hi = torch.maximum(x.detach().reshape(-1, D).amax(0), y.detach().reshape(-1, D).amax(0))
+        r = torch.cat([lo, -hi]).float()
+        if dp_active():
+            dist.all_reduce(r, op=dist.ReduceOp.MIN)
+        return torch.cat([r[:D], -r[D:]])
     lo = torch.minimum(x.detach().amin(), y.detach().amin())
     hi = torch.maximum(x.detach().amax(), y.detach().amax())
     r = torch.stack([lo, -hi]).float()
-    from ..._dist import dp_active
     if dp_active():
         dist.all_reduce(r, op=dist.ReduceOp.MIN)
     return torch.stack([r[0], -r[1]])
@@ -146,7 +170,11 @@ def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=T
     ``range_lo_hi``: device (2,) tensor from ``global_range`` -- the kernel folds it into its own scan.
     ``flags``: EML_SINKHORN_* of the C ABI; default: whatever the split kernel's watch says (``_SplitWatch``).
     ``rho``: reach**p of unbalanced OT, or None (balanced: the call is ``eml_sinkhorn_fwd_ex_f32``, as it always was);
-    ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when balanced)."""
+    ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when balanced).
+    ``x, y`` of shape ``(B, N)`` (1-D points) or ``(B, N, D)`` with ``D > 1`` (``eml_sinkhorn_fwd_dim_f32``)."""
+    if x.dim() == 3:
+        return _sinkhorn_raw_dim(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx, need_gy, out,
+                                 range_lo_hi, flags, rho, want_lam)
     L = _lib.lib()
     B, N = x.shape
     o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy)
@@ -175,32 +203,67 @@ def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=T
     return r
 
 
+def _sinkhorn_raw_dim(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx, need_gy, out, range_lo_hi, flags,
+                      rho, want_lam):
+    """``sinkhorn_raw`` for ``(B, N, D)`` points: one ``eml_sinkhorn_fwd_dim_f32`` call (the split kernel and its watch do
+    not apply; ``flags`` is passed through)."""
+    L = _lib.lib()
+    B, N, D = x.shape
+    o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy, D=D)
+    lam = None
+    if want_lam:
+        lam = o.get("lam")
+        lam = torch.empty(64, dtype=torch.float32, device=x.device) if lam is None else lam
+    _lib.check(L.eml_sinkhorn_fwd_dim_f32(
+        _lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
+        float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
+        _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]),
+        _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N, D, int(flags or 0),
+        float(rho) if rho is not None else 0.0, _lib.ptr(lam), _lib.current_stream()), "eml_sinkhorn_fwd_dim_f32")
+    r = {"loss": o["loss"], "gx": o["gx"], "gy": o["gy"], "eps_s": o["eps_s"], "n_eps": o["n_eps"],
+         "diameter": o["diameter"], "duals": o["work"][:4 * B * N].view(4, B, N), "work": o["work"]}
+    if lam is not None:
+        r["lam"] = lam
+    return r
+
+
 class _SinkhornDivergence(torch.autograd.Function):
     """loss (B,) = S_eps(alpha@x, beta@y).  Backward = analytic gradient of the last
-    extrapolation (``sinkhorn_divergence.py:101-107``), produced by the forward kernel.  ``rho``: reach**p or None."""
+    extrapolation (``sinkhorn_divergence.py:101-107``), produced by the forward kernel.  ``rho``: reach**p or None.
+    ``x, y``: (B, N) or (B, N, D).  Weights that require grad get ``gloss * (b_x - a_x)`` / ``gloss * (a_y - b_y)`` from the
+    final duals the forward left in its scratch (``eml_sinkhorn_bwd_weights_f32``)."""
 
     @staticmethod
     def forward(ctx, x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, range_lo_hi=None, rho=None):
         r = sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter,
                          ctx.needs_input_grad[0], ctx.needs_input_grad[1], range_lo_hi=range_lo_hi, rho=rho)
-        ctx.save_for_backward(r["gx"], r["gy"])
+        ctx.want_weights = (alpha is not None and ctx.needs_input_grad[2], beta is not None and ctx.needs_input_grad[3])
+        ctx.BN = (x.shape[0], x.shape[1])
+        ctx.save_for_backward(r["gx"], r["gy"], r["work"] if any(ctx.want_weights) else None)
         return r["loss"]
 
     @staticmethod
     def backward(ctx, gloss):
-        gx_u, gy_u = ctx.saved_tensors
+        gx_u, gy_u, work = ctx.saved_tensors
         L = _lib.lib()
         gloss = gloss.contiguous()
-        out = [None, None]
+        out = [None, None, None, None]
         for k, gu in enumerate((gx_u, gy_u)):
             if gu is None:
                 continue
-            B, N = gu.shape
+            B, N = gu.shape[0], gu[0].numel()   # (B, N) or (B, N, D): the same row scaling
             go = torch.empty_like(gu)
             _lib.check(L.eml_sinkhorn_bwd_f32(_lib.ptr(gloss), _lib.ptr(gu), _lib.ptr(go), B, N,
                                               _lib.current_stream()), "eml_sinkhorn_bwd_f32")
             out[k] = go
-        return out[0], out[1], None, None, None, None, None, None, None, None, None, None
+        if work is not None:
+            B, N = ctx.BN
+            ga = torch.empty(B, N, dtype=torch.float32, device=gloss.device) if ctx.want_weights[0] else None
+            gb = torch.empty(B, N, dtype=torch.float32, device=gloss.device) if ctx.want_weights[1] else None
+            _lib.check(L.eml_sinkhorn_bwd_weights_f32(_lib.ptr(gloss), _lib.ptr(work), _lib.ptr(ga), _lib.ptr(gb), B, N,
+                                                      _lib.current_stream()), "eml_sinkhorn_bwd_weights_f32")
+            out[2], out[3] = ga, gb
+        return out[0], out[1], out[2], out[3], None, None, None, None, None, None, None, None
 
 
 class SamplesLoss(Module):
@@ -208,7 +271,8 @@ class SamplesLoss(Module):
 
     ``SamplesLoss(loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5,
     batchsize=None)`` -- reference signature ``samples_loss.py:22``; ``forward(x, y)`` with
-    ``x, y`` of shape ``(B, N, 1)`` returns ``(B,)`` (``samples_loss.py:35-46``).
+    ``x, y`` of shape ``(B, N, D)``, ``1 <= D <= 8``, returns ``(B,)`` (``samples_loss.py:35-46``); the gradients have
+    the shape of ``x``, ``y``.  In the four- and six-argument forms, weights that require grad get gradients too.
 
     ``reach``: None (balanced OT) or a number > 0 (``float('inf')`` included; anything else raises ``ValueError``).
     With a reach, every softmin of the Sinkhorn loop is damped by ``1 / (1 + eps / reach**p)`` as in EMLight's fork
@@ -269,11 +333,20 @@ class SamplesLoss(Module):
             return None, x, None, y  # uniform 1/N weights are generated inside the kernel
         raise ValueError("A SamplesLoss accepts two (x, y), four (a, x, b, y) or six (l_x, a, x, l_y, b, y) arguments.")
 
+    def _check_samples(self, x, y):
+        """The point dimension D of ``x, y`` (both ``(B, N, D)``, 1 <= D <= MAX_DIM), or ValueError."""
+        if x.dim() != 3 or y.shape != x.shape or x.shape[1] != self.N:
+            raise ValueError("expected x, y of the same shape (B, %d, D), got %s and %s"
+                             % (self.N, tuple(x.shape), tuple(y.shape)))
+        D = x.shape[-1]
+        if not 1 <= D <= MAX_DIM:
+            raise ValueError("the point dimension D must be 1 <= D <= %d (EML_SINKHORN_MAX_DIM), got D = %d" % (MAX_DIM, D))
+        return D
+
     def forward(self, *args):
         a, x, b, y = self.process_args(*args)
-        if x.dim() != 3 or x.shape[-1] != 1 or y.shape != x.shape or x.shape[1] != self.N:
-            raise ValueError("expected x, y of shape (B, %d, 1), got %s and %s"
-                             % (self.N, tuple(x.shape), tuple(y.shape)))
+        if self._check_samples(x, y) > 1:
+            return self._forward_dim(a, x, b, y)
         B = x.shape[0]
         x2 = _lib.require_gpu_tensor(x.reshape(B, self.N), "x")
         y2 = _lib.require_gpu_tensor(y.reshape(B, self.N), "y")
@@ -285,9 +358,31 @@ class SamplesLoss(Module):
         rng = global_range(x2, y2) if (self.sync_diameter and self.diameter is None) else None
         return _SinkhornDivergence.apply(x2, y2, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
 
+    def _forward_dim(self, a, x, b, y):
+        """``forward`` on ``(B, N, D)`` samples, D > 1: gradients ``(B, N, D)``, the (2*D,) range under ``sync_diameter``."""
+        B = x.shape[0]
+        x3 = _lib.require_gpu_tensor(x, "x")
+        y3 = _lib.require_gpu_tensor(y, "y")
+        if B == 0:
+            return x3.new_zeros(0) + 0.0 * (x3.sum() + y3.sum())
+        a2 = None if a is None else _lib.require_gpu_tensor(a.reshape(B, self.N), "alpha")
+        b2 = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
+        M, Mt = self.cost_matrix(x3.device)
+        rng = global_range(x3, y3) if (self.sync_diameter and self.diameter is None) else None
+        return _SinkhornDivergence.apply(x3, y3, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
+
     def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None, want_lam=False):
         """Every device output of one call (loss, unit grads, schedule, duals; with ``want_lam`` the dampening schedule
-        ``lam`` next to ``eps_s``) -- for parity tests and timing."""
+        ``lam`` next to ``eps_s``) -- for parity tests and timing.  ``(B, N, D)`` samples with D > 1: gradients
+        ``(B, N, D)``."""
+        if x.dim() == 3 and x.shape[-1] > 1:
+            self._check_samples(x, y)
+            x3 = _lib.require_gpu_tensor(x, "x")
+            y3 = _lib.require_gpu_tensor(y, "y")
+            M, Mt = self.cost_matrix(x3.device)
+            rng = global_range(x3, y3) if (self.sync_diameter and self.diameter is None) else None
+            return sinkhorn_raw(x3, y3, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
+                                need_gx, need_gy, out, range_lo_hi=rng, flags=flags, rho=self.rho, want_lam=want_lam)
         B = x.shape[0]
         x2 = _lib.require_gpu_tensor(x.reshape(B, self.N), "x")
         y2 = _lib.require_gpu_tensor(y.reshape(B, self.N), "y")

@@ -40,6 +40,13 @@ SIGNATURES = {
                                         ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
                                         _int, ctypes.c_double, _f32p, _stream]),
     "eml_sinkhorn_bwd_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _stream]),
+    "eml_sinkhorn_dim_work_floats": (ctypes.c_size_t, [_int, _int, _int]),
+    "eml_sinkhorn_fwd_dim_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_double, ctypes.c_double, _int,
+                                        ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
+                                        _int, _int, ctypes.c_double, _f32p, _stream]),
+    "eml_sinkhorn_schedule_dim_f32": (_int, [_f32p, _f32p, ctypes.c_long, _int, ctypes.c_double, ctypes.c_double, _int,
+                                             ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _stream]),
+    "eml_sinkhorn_bwd_weights_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _int, _int, _stream]),
     # the generator's L1-type loss terms (host pointer arrays: ctypes arrays of c_void_p / c_long / c_int / c_float)
     "eml_l1_pairs_partial_doubles": (ctypes.c_size_t, [_int]),
     "eml_l1_pairs_fwd_f32": (_int, [_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

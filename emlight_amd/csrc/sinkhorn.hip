@@ -82,13 +82,15 @@ struct ScanHead {
   float4 a, c, a2, c2;
   float rlo, rhi;   // range of x U y on the OTHER ranks (all-reduced by the caller), or +inf / -inf
 };
-template <int kWG>
+// kD > 1 (D-dimensional points): no early request -- device_schedule scans the D components itself.
+template <int kWG, int kD = 1>
 __device__ __forceinline__ ScanHead schedule_scan_begin(const float* __restrict__ x, const float* __restrict__ y, int B,
                                                         int N, double diameter, const float* __restrict__ range_dev) {
   ScanHead h;
   h.a = h.c = h.a2 = h.c2 = make_float4(0.f, 0.f, 0.f, 0.f);
   h.rlo = INFINITY;
   h.rhi = -INFINITY;
+  if constexpr (kD > 1) return h;
   if (diameter <= 0.0 && range_dev) {   // data-parallel ranks: the diameter is the range over the GLOBAL batch
     h.rlo = range_dev[0];
     h.rhi = range_dev[1];
@@ -106,17 +108,52 @@ __device__ __forceinline__ ScanHead schedule_scan_begin(const float* __restrict_
   return h;
 }
 
-template <int kWG, bool kFinalBarrier = true>
+// kD > 1: x, y are (B,N,dim) points (dim <= kD); the diameter is ||max - min||_2 over the per-component ranges of x U y
+// (sinkhorn_divergence.py:9-18), the f32 differences squared and summed in f64; range_dev then holds 2*dim floats
+// (dim minima, then dim maxima).
+template <int kWG, bool kFinalBarrier = true, int kD = 1>
 __device__ __forceinline__ void device_schedule(const ScanHead& head, const float* __restrict__ x,
                                                 const float* __restrict__ y, int B, int N,
                                                 double blur, double log_blur, double log_scaling, int p_exp,
                                                 double diameter, double rho, float* eps_l, float* lam_l,
                                                 int* n_eps_l, float* __restrict__ eps_out, int* __restrict__ n_eps_out,
-                                                float* __restrict__ diameter_out, float* __restrict__ lam_out) {
+                                                float* __restrict__ diameter_out, float* __restrict__ lam_out,
+                                                const float* __restrict__ range_dev = nullptr, int dim = 1) {
   __shared__ float red_lo[16], red_hi[16];
   const int tid0 = threadIdx.x;
   float lo = INFINITY, hi = -INFINITY;
-  if (diameter <= 0.0) {
+  if constexpr (kD > 1) {
+    if (diameter <= 0.0) {
+      // thread t < S scans component t % dim of the flat (B*N*dim) arrays (S = a multiple of dim: the component is fixed)
+      __shared__ float part_lo[kWG], part_hi[kWG];
+      const long n_all = (long)B * N * dim;
+      const int S = (kWG / dim) * dim;
+      if (tid0 < S) {
+        for (long k = tid0; k < n_all; k += S) {
+          lo = fminf(lo, fminf(x[k], y[k]));
+          hi = fmaxf(hi, fmaxf(x[k], y[k]));
+        }
+      }
+      part_lo[tid0] = lo;
+      part_hi[tid0] = hi;
+      __syncthreads();
+      const int w = tid0 >> 6, l = tid0 & 63;
+      if (w < dim) {   // wave w folds component w
+        lo = INFINITY;
+        hi = -INFINITY;
+        for (int t = w + dim * l; t < S; t += 64 * dim) {
+          lo = fminf(lo, part_lo[t]);
+          hi = fmaxf(hi, part_hi[t]);
+        }
+        lo = eml::wave_min_dpp(lo);
+        hi = eml::wave_max_dpp(hi);
+        if (l == 0) {
+          red_lo[w] = range_dev ? fminf(lo, range_dev[w]) : lo;
+          red_hi[w] = range_dev ? fmaxf(hi, range_dev[dim + w]) : hi;
+        }
+      }
+    }
+  } else if (diameter <= 0.0) {
     const long n_all = (long)B * N, n4 = n_all >> 2;
     const float4* x4 = reinterpret_cast<const float4*>(x);
     const float4* y4 = reinterpret_cast<const float4*>(y);
@@ -152,7 +189,14 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
   // redundantly by all 16 waves it held every SIMD for ~3 us of a 25 us kernel; the other waves go on to their staging
   if (tid0 < 64) {
     double d = diameter;
-    if (diameter <= 0.0) {
+    if (kD > 1 && diameter <= 0.0) {
+      double s2 = 0.0;
+      for (int c = 0; c < dim; ++c) {
+        const double r = (double)(red_hi[c] - red_lo[c]);   // f32 subtraction, as maxs - mins
+        s2 += r * r;
+      }
+      d = sqrt(s2);
+    } else if (diameter <= 0.0) {
       lo = red_lo[0];
       hi = red_hi[0];
 #pragma unroll
@@ -192,23 +236,33 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
   if (kFinalBarrier) __syncthreads();   // otherwise the caller's next barrier publishes eps_l / lam_l / n_eps_l
 }
 
-// threads per softmin group: cached kernel 512 (128 rows x 4 lanes), stream kernel 256 (row per thread)
-template <bool kCached>
+// threads per softmin group: cached kernel 512 (128 rows x 4 lanes), stream kernel 256 (row per thread).
+// kD > 1: x, y are (B,N,dim) points (dim <= kD; the components past dim are zero) and C_ij = .5*(.1*(|p_i|^2 - 2 p_i.q_j +
+// |q_j|^2) + M_ij) (utils.py:85-99).  The cached kernel stages the points component-major (pts [2][kD][NP]) with their
+// squared norms (nrm [2][NP]); the costs are built once, so only its prologue and its last sweep (kD expectation rows)
+// change.  The stream kernel recomputes the cost per element (kD fmas on the row's point in registers): its column points
+// are read straight from x / y (one wave-uniform address per column; at N = 2048 the component-major copy would not fit
+// the LDS next to the dual vectors), only their norms are staged.
+template <bool kCached, int kD = 1>
 __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ M,
     const float* __restrict__ Mt, const float* __restrict__ alpha, const float* __restrict__ beta,
     double blur, double log_blur, double log_scaling, int p_exp, double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out,
     int* __restrict__ n_eps_out, float* __restrict__ diameter_out, double rho, float* __restrict__ lam_out,
-    float* __restrict__ work /* (8,B,N): duals a_x,b_y,a_y,b_x then E rows */, int B, int N) {
+    float* __restrict__ work /* (8,B,N): duals a_x,b_y,a_y,b_x then E rows; kD > 1: (4,B,N) duals, (4,B,N,dim) E rows */,
+    int B, int N, int dim) {
   constexpr int kGT = kCached ? 512 : 256;  // threads per softmin group
   constexpr int kWG = 2 * kGT;              // two groups per workgroup
+  // LDS vectors ahead of lw2: pts (kD = 1); pts + nrm (cached, kD > 1); nrm (stream, kD > 1)
+  constexpr int kPtsVecs = kD == 1 ? 2 : (kCached ? 2 * kD + 2 : 2);
   __shared__ float eps_l[EML_MAX_EPS];
   __shared__ float lam_l[EML_MAX_EPS];
   __shared__ int n_eps_l;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int NP = round_up4(N) + kJPT;
   float* pts = smem;
-  float* lw2 = pts + 2 * NP;
+  float* nrm = kCached ? pts + 2 * kD * NP : smem;   // kD > 1: |p|^2 of every point, [2][NP]
+  float* lw2 = pts + kPtsVecs * NP;
   float* h2 = lw2 + 2 * NP;
   float* potl = h2 + 4 * NP;
   float* Ml = potl + 2 * NP;
@@ -231,6 +285,9 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
   constexpr int kMPT = kCached ? (4 * kCJ) * (4 * kCJ) / kWG : 1;   // 16 elements of M per thread
   float mreg[kMPT];
   float my_p = 0.f, my_w = unif;
+  float my_pd[kD];   // kD > 1: the point's components
+#pragma unroll
+  for (int d = 0; d < kD; ++d) my_pd[d] = 0.f;
   if constexpr (kCached) {
     const int nn = N * N;
     // (4-byte loads on purpose: staged as four float4 per thread the same 64 KB arrived 1.2 us later -- measured)
@@ -239,13 +296,20 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     if (tid < 2 * NP) {   // 2 * NP <= 384 < kWG
       const int which = tid >= NP, k = tid - which * NP;
       if (k < N) {
-        my_p = (which == 0 ? x : y)[(size_t)b * N + k];
+        if constexpr (kD == 1) {
+          my_p = (which == 0 ? x : y)[(size_t)b * N + k];
+        } else {
+          const float* src = (which == 0 ? x : y) + ((size_t)b * N + k) * dim;
+#pragma unroll
+          for (int d = 0; d < kD; ++d)
+            if (d < dim) my_pd[d] = src[d];
+        }
         const float* wp = which == 0 ? alpha : beta;
         if (wp) my_w = wp[(size_t)b * N + k];
       }
     }
   }
-  const ScanHead scan_head = schedule_scan_begin<kWG>(x, y, B, N, diameter, range_dev);   // requested; folded in device_schedule
+  const ScanHead scan_head = schedule_scan_begin<kWG, kD>(x, y, B, N, diameter, range_dev);   // requested; folded in device_schedule
   if constexpr (kCached) {
     // staging runs WHILE the scan is in flight (the M / point loads were issued first, so they land first): points,
     // log-weights, h buffer 0 = log w of each group's columns (sweep 0 reads h = log w, potentials are zero:
@@ -253,7 +317,18 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     if (tid < 2 * NP) {
       const int k = tid - (tid >= NP) * NP;
       const float l = (k < N) ? ((my_w > 0.f) ? logf(my_w) : -100000.0f) : 0.f;  // sinkhorn_divergence.py:47-50
-      pts[tid] = my_p;
+      if constexpr (kD == 1) {
+        pts[tid] = my_p;
+      } else {
+        const int which = tid >= NP;
+        float n2 = 0.f;
+#pragma unroll
+        for (int d = 0; d < kD; ++d) {
+          pts[(which * kD + d) * NP + k] = my_pd[d];
+          n2 = fmaf(my_pd[d], my_pd[d], n2);
+        }
+        nrm[tid] = n2;
+      }
       lw2[tid] = l * kLog2e;
       h2[tid] = l * kLog2e;        // h2[0][gl = which][k]
       h2[2 * NP + tid] = 0.f;
@@ -282,8 +357,8 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     }
     EML_STAMP(1);   // this thread's staging written
   }
-  device_schedule<kWG, !kCached>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, rho, eps_l, lam_l, &n_eps_l,
-                                 eps_out, n_eps_out, diameter_out, lam_out);
+  device_schedule<kWG, !kCached, kD>(scan_head, x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter, rho, eps_l, lam_l,
+                                     &n_eps_l, eps_out, n_eps_out, diameter_out, lam_out, range_dev, dim);
   const float* eps_s = eps_l;
 
   // ---- stream kernel: stage points and log-weights; h buffer 0 = log w of each group's columns, buffer 1 zeroed
@@ -292,20 +367,29 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
       const int which = i / NP, k = i - which * NP;
       float p = 0.f, l = 0.f;
       if (k < N) {
-        p = (which == 0 ? x : y)[(size_t)b * N + k];
+        if constexpr (kD == 1) {
+          p = (which == 0 ? x : y)[(size_t)b * N + k];
+        } else {
+          const float* src = (which == 0 ? x : y) + ((size_t)b * N + k) * dim;
+          for (int d = 0; d < dim; ++d) p = fmaf(src[d], src[d], p);   // |p|^2
+        }
         const float* wp = which == 0 ? alpha : beta;
         const float w = wp ? wp[(size_t)b * N + k] : unif;
         l = (w > 0.f) ? logf(w) : -100000.0f;  // sinkhorn_divergence.py:47-50
       }
-      pts[i] = p;
+      pts[i] = p;   // kD > 1: nrm (aliases pts)
       lw2[i] = l * kLog2e;
       h2[i] = l * kLog2e;
       h2[2 * NP + i] = 0.f;
     }
   }
 
-  const float* P = pts + (rows_x ? 0 : NP);
-  const float* Q = pts + (cols_x ? 0 : NP);
+  const float* P = pts + (rows_x ? 0 : kD * NP);
+  const float* Q = pts + (cols_x ? 0 : kD * NP);
+  const float* nrm_rows = nrm + (rows_x ? 0 : NP);   // kD > 1
+  const float* nrm_cols = nrm + (cols_x ? 0 : NP);
+  const float* xg_rows = (rows_x ? x : y) + (size_t)b * N * dim;   // stream kernel, kD > 1: the points in global memory
+  const float* xg_cols = (cols_x ? x : y) + (size_t)b * N * dim;
   const float* lw2_rows = lw2 + (rows_x ? 0 : NP);
   const float* lw2_cols = lw2 + (cols_x ? 0 : NP);
 
@@ -328,20 +412,46 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     const int cnt = (i < N) ? max(0, min(split, N - jbase)) : 0;
     owner = (quarter == 0) && (i < N);
     const int ic = min(i, N - 1);
-    const float pi = P[ic];
     const float4* mrow = reinterpret_cast<const float4*>(Ml + ic * ldm + jbase);
-    const float4* qrow = reinterpret_cast<const float4*>(Q + jbase);
+    if constexpr (kD == 1) {
+      const float pi = P[ic];
+      const float4* qrow = reinterpret_cast<const float4*>(Q + jbase);
 #pragma unroll
-    for (int q = 0; q < kCJ / 4; ++q) {
-      const float4 mv = mrow[q];
-      const float4 qv = qrow[q];
-      // cost_ij on register pairs (v_pk_mul / v_pk_fma): 4 waves per SIMD build 32 costs per thread here
-      const v2f p2 = v2f{pi, pi};
-      const v2f qa = v2f{qv.x, qv.y}, qb = v2f{qv.z, qv.w};
-      const v2f ca = ((p2 * p2 - 2.0f * (p2 * qa) + qa * qa) * 0.1f + v2f{mv.x, mv.y}) * 0.5f;
-      const v2f cb = ((p2 * p2 - 2.0f * (p2 * qb) + qb * qb) * 0.1f + v2f{mv.z, mv.w}) * 0.5f;
-      c2[2 * q + 0] = v2f{(4 * q + 0 < cnt) ? ca.x : kBig, (4 * q + 1 < cnt) ? ca.y : kBig};
-      c2[2 * q + 1] = v2f{(4 * q + 2 < cnt) ? cb.x : kBig, (4 * q + 3 < cnt) ? cb.y : kBig};
+      for (int q = 0; q < kCJ / 4; ++q) {
+        const float4 mv = mrow[q];
+        const float4 qv = qrow[q];
+        // cost_ij on register pairs (v_pk_mul / v_pk_fma): 4 waves per SIMD build 32 costs per thread here
+        const v2f p2 = v2f{pi, pi};
+        const v2f qa = v2f{qv.x, qv.y}, qb = v2f{qv.z, qv.w};
+        const v2f ca = ((p2 * p2 - 2.0f * (p2 * qa) + qa * qa) * 0.1f + v2f{mv.x, mv.y}) * 0.5f;
+        const v2f cb = ((p2 * p2 - 2.0f * (p2 * qb) + qb * qb) * 0.1f + v2f{mv.z, mv.w}) * 0.5f;
+        c2[2 * q + 0] = v2f{(4 * q + 0 < cnt) ? ca.x : kBig, (4 * q + 1 < cnt) ? ca.y : kBig};
+        c2[2 * q + 1] = v2f{(4 * q + 2 < cnt) ? cb.x : kBig, (4 * q + 3 < cnt) ? cb.y : kBig};
+      }
+    } else {
+      // the D-term cost: |p|^2 and |q|^2 from the staged norms, p.q as kD fmas per element (zero components add nothing)
+      float pd[kD];
+#pragma unroll
+      for (int d = 0; d < kD; ++d) pd[d] = P[d * NP + ic];
+      const v2f pp = v2f{nrm_rows[ic], nrm_rows[ic]};
+      const float4* nrow = reinterpret_cast<const float4*>(nrm_cols + jbase);
+#pragma unroll
+      for (int q = 0; q < kCJ / 4; ++q) {
+        const float4 mv = mrow[q];
+        const float4 nv = nrow[q];
+        v2f da = v2f{0.f, 0.f}, db = da;
+#pragma unroll
+        for (int d = 0; d < kD; ++d) {
+          const float4 qv = reinterpret_cast<const float4*>(Q + d * NP + jbase)[q];
+          const v2f p2 = v2f{pd[d], pd[d]};
+          da = p2 * v2f{qv.x, qv.y} + da;
+          db = p2 * v2f{qv.z, qv.w} + db;
+        }
+        const v2f ca = ((pp - 2.0f * da + v2f{nv.x, nv.y}) * 0.1f + v2f{mv.x, mv.y}) * 0.5f;
+        const v2f cb = ((pp - 2.0f * db + v2f{nv.z, nv.w}) * 0.1f + v2f{mv.z, mv.w}) * 0.5f;
+        c2[2 * q + 0] = v2f{(4 * q + 0 < cnt) ? ca.x : kBig, (4 * q + 1 < cnt) ? ca.y : kBig};
+        c2[2 * q + 1] = v2f{(4 * q + 2 < cnt) ? cb.x : kBig, (4 * q + 3 < cnt) ? cb.y : kBig};
+      }
     }
   }
   if constexpr (!kCached) __syncthreads();   // (the cached kernel's barrier sits after its M staging)
@@ -351,6 +461,7 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
   const size_t plane = (size_t)B * N;
   float* fin_out = work + (size_t)g * plane + (size_t)b * N;        // a_x | b_y | a_y | b_x
   float* e_out = work + (size_t)(4 + g) * plane + (size_t)b * N;    // E_i[q] of the last softmax
+  float* e_out_d = work + 4 * plane + ((size_t)g * plane + (size_t)b * N) * dim;   // kD > 1: E_i[q] rows (N, dim)
 
   float pot = 0.f;  // this row's potential (cached kernel)
   for (int s = 0; s < n_eps + 2; ++s) {
@@ -397,7 +508,7 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
           sB += v2f{__builtin_amdgcn_exp2f(dB.x), __builtin_amdgcn_exp2f(dB.y)};
         }
         sum = (sA.x + sA.y) + (sB.x + sB.y);
-      } else {
+      } else if constexpr (kD == 1) {
         const float4* qrow = reinterpret_cast<const float4*>(Q + jbase);
 #pragma unroll
         for (int q = 0; q < kCJ / 4; ++q) {
@@ -412,6 +523,33 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
         }
         tq += eml::lane_xor1(tq);
         tq += eml::lane_xor2(tq);
+      } else {   // kD expectation rows E_i[q_d]: the exponentials replace the exponents in t2, then one row at a time
+#pragma unroll
+        for (int q = 0; q < kCJ / 4; ++q) {
+          const v2f dA = t2[2 * q + 0] - mm, dB = t2[2 * q + 1] - mm;
+          const float e0 = __builtin_amdgcn_exp2f(dA.x);
+          const float e1 = __builtin_amdgcn_exp2f(dA.y);
+          const float e2 = __builtin_amdgcn_exp2f(dB.x);
+          const float e3 = __builtin_amdgcn_exp2f(dB.y);
+          sum += (e0 + e1) + (e2 + e3);
+          t2[2 * q + 0] = v2f{e0, e1};
+          t2[2 * q + 1] = v2f{e2, e3};
+        }
+        float s4 = sum;
+        s4 += eml::lane_xor1(s4);
+        s4 += eml::lane_xor2(s4);
+        for (int d = 0; d < dim; ++d) {
+          const float4* qrow = reinterpret_cast<const float4*>(Q + d * NP + jbase);
+          float tqd = 0.f;
+#pragma unroll
+          for (int q = 0; q < kCJ / 4; ++q) {
+            const float4 qv = qrow[q];
+            tqd = fmaf(t2[2 * q].x, qv.x, fmaf(t2[2 * q].y, qv.y, fmaf(t2[2 * q + 1].x, qv.z, fmaf(t2[2 * q + 1].y, qv.w, tqd))));
+          }
+          tqd += eml::lane_xor1(tqd);
+          tqd += eml::lane_xor2(tqd);
+          if (owner) e_out_d[i * dim + d] = lam_l[k_eps] * (tqd / s4);
+        }
       }
       sum += eml::lane_xor1(sum);
       sum += eml::lane_xor2(sum);
@@ -420,13 +558,13 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
       if (final_sweep) {
         if (owner) {
           fin_out[i] = sm;
-          e_out[i] = lam_l[k_eps] * (tq / sum);   // lam_last-scaled expectation row: the gradient of lam * softmin
+          if constexpr (kD == 1) e_out[i] = lam_l[k_eps] * (tq / sum);   // lam_last-scaled expectation row: the gradient of lam * softmin
         }
       } else {
         pot = (s == 0) ? sm : 0.5f * (pot + sm);  // symmetrised update, sinkhorn_divergence.py:96-97
         if (owner) hdst[i] = fmaf(pot, k_next, lw2_rows[i]);
       }
-    } else {
+    } else if constexpr (kD == 1) {
       for (int r = t; r < N; r += kGT) {
         const float pi = P[r];
         float m = -INFINITY;
@@ -452,6 +590,46 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
           hdst[r] = fmaf(pr, k_next, lw2_rows[r]);
         }
       }
+    } else {
+      for (int r = t; r < N; r += kGT) {
+        float pd[kD];
+#pragma unroll
+        for (int d = 0; d < kD; ++d) pd[d] = (d < dim) ? xg_rows[(size_t)r * dim + d] : 0.f;
+        const float pp = nrm_rows[r];
+        auto cost = [&](int j) {
+          const float* qj = xg_cols + (size_t)j * dim;
+          float dot = 0.f;
+#pragma unroll
+          for (int d = 0; d < kD; ++d)
+            if (d < dim) dot = fmaf(pd[d], qj[d], dot);
+          return ((pp - 2.0f * dot + nrm_cols[j]) * 0.1f + Mt[(size_t)j * N + r]) * 0.5f;
+        };
+        float m = -INFINITY;
+        for (int j = 0; j < N; ++j) m = fmaxf(m, fmaf(cost(j), nie2, hsrc[j]));
+        float sum = 0.f, tqd[kD];
+#pragma unroll
+        for (int d = 0; d < kD; ++d) tqd[d] = 0.f;
+        for (int j = 0; j < N; ++j) {
+          const float e = __builtin_amdgcn_exp2f(fmaf(cost(j), nie2, hsrc[j] - m));
+          sum += e;
+          if (final_sweep) {
+#pragma unroll
+            for (int d = 0; d < kD; ++d)
+              if (d < dim) tqd[d] = fmaf(e, xg_cols[(size_t)j * dim + d], tqd[d]);
+          }
+        }
+        const float sm = neg_eps_lam * kLn2 * (m + __builtin_amdgcn_logf(sum));
+        if (final_sweep) {
+          fin_out[r] = sm;
+#pragma unroll
+          for (int d = 0; d < kD; ++d)
+            if (d < dim) e_out_d[(size_t)r * dim + d] = lam_l[k_eps] * (tqd[d] / sum);
+        } else {
+          const float pr = (s == 0) ? sm : 0.5f * (potl[gl * NP + r] + sm);
+          potl[gl * NP + r] = pr;
+          hdst[r] = fmaf(pr, k_next, lw2_rows[r]);
+        }
+      }
     }
     __syncthreads();
     if constexpr (kCached) EML_STAMP(4 + s);   // sweep s done
@@ -464,13 +642,18 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
 // into a running (max, sum) pair -- an online log-sum-exp, one pass per sweep instead of the stream kernel's two passes
 // over an L2-resident Mt.  The tile sequence is the same in every sweep, so the next tile's global loads are always in
 // flight during the current tile's arithmetic, across sweep boundaries too.  One LDS-only barrier per tile.
-template <int LPR /* lanes per row: 2 (N <= 256) or 1 (N <= 512) */>
+// kD > 1 (D-dimensional points, dim <= kD, the components past dim zero): the points are staged component-major
+// (pts [2][kD][NP]), qq holds .05 |q|^2, and the exponent's p.q term costs kD packed fmas per column pair instead of one --
+// the cost is recomputed per element here anyway, so per-element D-term distances need no per-call cost build (that would
+// be B*N^2 floats of scratch per problem, written and re-read every sweep).  The last sweep keeps kD expectation rows.
+template <int LPR /* lanes per row: 2 (N <= 256) or 1 (N <= 512) */, int kD = 1>
 __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ M,
     const float* __restrict__ alpha, const float* __restrict__ beta, double blur, double log_blur, double log_scaling,
     int p_exp,
     double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out, int* __restrict__ n_eps_out, float* __restrict__ diameter_out,
-    double rho, float* __restrict__ lam_out, float* __restrict__ work, int B, int N, const int* __restrict__ only_if) {
+    double rho, float* __restrict__ lam_out, float* __restrict__ work, int B, int N, const int* __restrict__ only_if,
+    int dim) {
   // `only_if` (device, may be NULL): the RESCUE launch behind the split kernel -- it returns at once unless the split
   // kernel raised its status word (a slice never saw its partners), in which case it recomputes the whole batch here
   if (only_if && __hip_atomic_load(only_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -481,13 +664,14 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
   __shared__ float eps_l[EML_MAX_EPS];
   __shared__ float lam_l[EML_MAX_EPS];
   __shared__ int n_eps_l;
-  device_schedule<kWG>(schedule_scan_begin<kWG>(x, y, B, N, diameter, range_dev), x, y, B, N, blur, log_blur, log_scaling, p_exp, diameter,
-                       rho, eps_l, lam_l, &n_eps_l, eps_out, n_eps_out, diameter_out, lam_out);
+  device_schedule<kWG, true, kD>(schedule_scan_begin<kWG, kD>(x, y, B, N, diameter, range_dev), x, y, B, N, blur, log_blur,
+                                 log_scaling, p_exp, diameter, rho, eps_l, lam_l, &n_eps_l, eps_out, n_eps_out, diameter_out,
+                                 lam_out, range_dev, dim);
   const float* eps_s = eps_l;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int NP = round_up4(N) + kJPT;
-  float* pts = smem;
-  float* lw2 = pts + 2 * NP;
+  float* pts = smem;                       // [2][kD][NP]
+  float* lw2 = pts + 2 * kD * NP;
   float* h2 = lw2 + 2 * NP;
   float* qq = h2 + 4 * NP;                 // [2][NP]: 0.05 * point^2 (the column-only term of the cost), pads zero
   float* Mtile = qq + 2 * NP;              // [2][NR][TS]
@@ -503,19 +687,31 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
     const int which = i / NP, k = i - which * NP;
     float p = 0.f, l = 0.f;
     if (k < N) {
-      p = (which == 0 ? x : y)[(size_t)b * N + k];
+      if constexpr (kD == 1) {
+        p = (which == 0 ? x : y)[(size_t)b * N + k];
+      } else {
+        const float* src = (which == 0 ? x : y) + ((size_t)b * N + k) * dim;
+        for (int d = 0; d < dim; ++d) p = fmaf(src[d], src[d], p);   // |p|^2
+      }
       const float* wp = which == 0 ? alpha : beta;
       const float w = wp ? wp[(size_t)b * N + k] : unif;
       l = (w > 0.f) ? logf(w) : -100000.0f;
     }
-    pts[i] = p;
-    qq[i] = 0.05f * p * p;
+    if constexpr (kD == 1) {
+      pts[i] = p;
+      qq[i] = 0.05f * p * p;
+    } else {
+#pragma unroll
+      for (int d = 0; d < kD; ++d)
+        pts[(which * kD + d) * NP + k] = (k < N && d < dim) ? (which == 0 ? x : y)[((size_t)b * N + k) * dim + d] : 0.f;
+      qq[i] = 0.05f * p;
+    }
     lw2[i] = l * kLog2e;
   }
   for (int i = tid; i < 4 * NP; i += kWG) h2[i] = 0.f;
   __syncthreads();
-  const float* P = pts + (rows_x ? 0 : NP);
-  const float* Q = pts + (cols_x ? 0 : NP);
+  const float* P = pts + (rows_x ? 0 : kD * NP);
+  const float* Q = pts + (cols_x ? 0 : kD * NP);
   const float* lw2_rows = lw2 + (rows_x ? 0 : NP);
   const float* lw2_cols = lw2 + (cols_x ? 0 : NP);
   const float* QQ = qq + (cols_x ? 0 : NP);
@@ -530,6 +726,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
   const bool owner = part == 0 && i < N;
   const int ic = min(i, N - 1);
   const float pi = P[ic];
+  const float* QQ_rows = qq + (rows_x ? 0 : NP);
   const int ntiles = (N + TJ - 1) / TJ;
   // staging role: row srow, 8 consecutive columns of the tile
   const int srow = tid / (TJ / 8), sq = tid % (TJ / 8);
@@ -566,6 +763,9 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
     const float* hsrc = h2 + (s & 1) * 2 * NP + gl * NP;
     float* hdst = h2 + ((s + 1) & 1) * 2 * NP + consumer_l * NP;
     float m_run = -INFINITY, s_run = 0.f, tq_run = 0.f;
+    float tq_rund[kD];   // kD > 1
+#pragma unroll
+    for (int d = 0; d < kD; ++d) tq_rund[d] = 0.f;
     for (int tile = 0; tile < ntiles; ++tile) {
       stage_load(tile + 1 < ntiles ? tile + 1 : 0);   // wraps: the first tile of the next sweep
       __builtin_amdgcn_sched_barrier(0);
@@ -580,13 +780,39 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
       v2f tv[8];
       const v2f dd = v2f{-0.1f * nie2 * pi, -0.1f * nie2 * pi}, ee = v2f{0.5f * nie2, 0.5f * nie2};
       v2f mA = v2f{-INFINITY, -INFINITY}, mB = mA;
+      if constexpr (kD > 1) {   // (-.1 n p_i).q_j: one packed fma per component and column pair, a component at a time
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float4 hv = *reinterpret_cast<const float4*>(hsrc + j0 + 4 * u);
+          tv[2 * u + 0] = v2f{hv.x, hv.y};
+          tv[2 * u + 1] = v2f{hv.z, hv.w};
+        }
+#pragma unroll 1
+        for (int d = 0; d < dim; ++d) {
+          const float c = -0.1f * nie2 * P[d * NP + ic];
+          const v2f cd = v2f{c, c};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float4 qd = *reinterpret_cast<const float4*>(Q + d * NP + j0 + 4 * u);
+            tv[2 * u + 0] = cd * v2f{qd.x, qd.y} + tv[2 * u + 0];
+            tv[2 * u + 1] = cd * v2f{qd.z, qd.w} + tv[2 * u + 1];
+          }
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float4 mv = *reinterpret_cast<const float4*>(mt + 4 * u);
         const float4 qv = *reinterpret_cast<const float4*>(Q + j0 + 4 * u);      // pads of pts / qq / h2 are zero-filled
         const float4 hv = *reinterpret_cast<const float4*>(hsrc + j0 + 4 * u);   // A_j (see the h2 initialisation)
         const bool jv = j0 + 4 * u < N;
-        const v2f b0 = dd * v2f{qv.x, qv.y} + v2f{hv.x, hv.y}, b1 = dd * v2f{qv.z, qv.w} + v2f{hv.z, hv.w};
+        v2f b0, b1;
+        if constexpr (kD == 1) {
+          b0 = dd * v2f{qv.x, qv.y} + v2f{hv.x, hv.y};
+          b1 = dd * v2f{qv.z, qv.w} + v2f{hv.z, hv.w};
+        } else {   // the brackets A_j + (-.1 n p_i).q_j, formed above
+          b0 = tv[2 * u + 0];
+          b1 = tv[2 * u + 1];
+        }
         const v2f ninf = v2f{-INFINITY, -INFINITY};
         tv[2 * u + 0] = jv ? ee * v2f{mv.x, mv.y} + b0 : ninf;
         tv[2 * u + 1] = jv ? ee * v2f{mv.z, mv.w} + b1 : ninf;
@@ -604,6 +830,25 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
           const v2f d = tv[u] - mm;
           sA += __builtin_amdgcn_exp2f(d.x);
           sB += __builtin_amdgcn_exp2f(d.y);
+        }
+      } else if constexpr (kD > 1) {   // the exponentials replace the exponents in tv, then one component at a time
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const v2f d = tv[u] - mm;
+          const float e0 = __builtin_amdgcn_exp2f(d.x), e1 = __builtin_amdgcn_exp2f(d.y);
+          sA += e0;
+          sB += e1;
+          tv[u] = v2f{e0, e1};
+        }
+#pragma unroll
+        for (int c = 0; c < kD; ++c) {
+          float qa = 0.f, qb = 0.f;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            qa = fmaf(tv[u].x, Q[c * NP + j0 + 2 * u], qa);
+            qb = fmaf(tv[u].y, Q[c * NP + j0 + 2 * u + 1], qb);
+          }
+          tq_rund[c] = fmaf(tq_rund[c], rescale, qa + qb);
         }
       } else {
 #pragma unroll
@@ -631,18 +876,33 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
       const float fa = __builtin_amdgcn_exp2f(m_run - m), fb = __builtin_amdgcn_exp2f(mo - m);
       sum = s_run * fa + so * fb;
       tq = tq_run * fa + qo * fb;
+      if constexpr (kD > 1) {
+#pragma unroll
+        for (int c = 0; c < kD; ++c) tq_rund[c] = tq_rund[c] * fa + eml::lane_xor1(tq_rund[c]) * fb;
+      }
     }
-    const float row_shift = 0.05f * nie2 * pi * pi;   // the row-only term of the exponents, left out of the tiles above
+    // the row-only term of the exponents, left out of the tiles above (kD > 1: n * .05 |p_i|^2)
+    const float row_shift = (kD == 1) ? 0.05f * nie2 * pi * pi : nie2 * QQ_rows[ic];
     const float sm = neg_eps_lam * kLn2 * ((m + row_shift) + __builtin_amdgcn_logf(sum));
     if (final_sweep) {
       if (owner) {
         fin_out[i] = sm;
-        e_out[i] = lam_l[k_eps] * (tq / sum);
+        if constexpr (kD == 1) {
+          e_out[i] = lam_l[k_eps] * (tq / sum);
+        } else {
+          float* e_row = work + 4 * plane + ((size_t)g * plane + (size_t)b * N + i) * dim;
+#pragma unroll
+          for (int c = 0; c < kD; ++c)
+            if (c < dim) e_row[c] = lam_l[k_eps] * (tq_rund[c] / sum);
+        }
       }
     } else {
       pot = (s == 0) ? sm : 0.5f * (pot + sm);
       // this row is a COLUMN of the group that reads hdst: fold its .05 p^2 term in with that sweep's n = -k_next
-      if (owner) hdst[i] = fmaf(pot, k_next, lw2_rows[i]) - k_next * (0.05f * pi * pi);
+      if (owner) {
+        if constexpr (kD == 1) hdst[i] = fmaf(pot, k_next, lw2_rows[i]) - k_next * (0.05f * pi * pi);
+        else hdst[i] = fmaf(pot, k_next, lw2_rows[i]) - k_next * QQ_rows[ic];
+      }
     }
     __syncthreads();
   }
@@ -885,9 +1145,11 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
 // xx / xy softmins and only through the cost's first argument (utils.py:88), and since the
 // softmax rows sum to one,  dL_b/dx_i = alpha_i * 0.1 * (E^xx_i[x] - E^xy_i[y])  (same for y).  Unbalanced OT multiplies
 // the last extrapolation by lam_last: the loop kernels' final sweep stores the E rows already scaled by it (1 when balanced).
+// kMultiDim (D-dimensional points): the E rows are (4,B,N,dim) and so are gx / gy, (B,N,dim): the same formula per component.
+template <bool kMultiDim>
 __global__ __launch_bounds__(256) void sinkhorn_finish_kernel(
     const float* __restrict__ work, const float* __restrict__ alpha, const float* __restrict__ beta,
-    float* __restrict__ loss, float* __restrict__ gx, float* __restrict__ gy, int B, int N) {
+    float* __restrict__ loss, float* __restrict__ gx, float* __restrict__ gy, int B, int N, int dim) {
   __shared__ float red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const size_t plane = (size_t)B * N, row = (size_t)b * N;
@@ -898,8 +1160,20 @@ __global__ __launch_bounds__(256) void sinkhorn_finish_kernel(
     const float a_x = work[o], b_y = work[plane + o], a_y = work[2 * plane + o], b_x = work[3 * plane + o];
     const float al = alpha ? alpha[o] : unif, be = beta ? beta[o] : unif;
     part += al * (b_x - a_x) + be * (a_y - b_y);
-    if (gx) gx[o] = al * 0.1f * (work[4 * plane + o] - work[7 * plane + o]);
-    if (gy) gy[o] = be * 0.1f * (work[5 * plane + o] - work[6 * plane + o]);
+    if constexpr (!kMultiDim) {
+      if (gx) gx[o] = al * 0.1f * (work[4 * plane + o] - work[7 * plane + o]);
+      if (gy) gy[o] = be * 0.1f * (work[5 * plane + o] - work[6 * plane + o]);
+    }
+  }
+  if constexpr (kMultiDim) {
+    const float* E = work + 4 * plane;
+    const size_t pd = plane * dim, rd = row * dim;
+    for (int k = tid; k < N * dim; k += 256) {
+      const size_t o = row + k / dim, e = rd + k;
+      const float al = alpha ? alpha[o] : unif, be = beta ? beta[o] : unif;
+      if (gx) gx[e] = al * 0.1f * (E[e] - E[3 * pd + e]);
+      if (gy) gy[e] = be * 0.1f * (E[pd + e] - E[2 * pd + e]);
+    }
   }
   part = eml::wave_sum(part);
   if ((tid & 63) == 0) red[tid >> 6] = part;
@@ -967,6 +1241,35 @@ __global__ __launch_bounds__(1024) void schedule_kernel(const float* __restrict_
   eps_out[k++] = (float)((p == 2) ? blur * blur : pow(blur, (double)p));
   *n_eps_out = k;
   for (; k < EML_MAX_EPS; ++k) eps_out[k] = 0.f;
+}
+
+// Diameter over D-dimensional points + epsilon schedule (eml_sinkhorn_schedule_dim_f32): the loop kernels' device_schedule
+// in one workgroup, the unused tail of eps_out zeroed as schedule_kernel does.
+__global__ __launch_bounds__(1024) void schedule_dim_kernel(const float* __restrict__ x, const float* __restrict__ y, int n,
+                                                            int dim, double blur, double log_blur, double log_scaling, int p,
+                                                            double diameter, const float* __restrict__ range_dev,
+                                                            float* __restrict__ eps_out, int* __restrict__ n_eps_out,
+                                                            float* __restrict__ diameter_out) {
+  __shared__ float eps_l[EML_MAX_EPS];
+  __shared__ float lam_l[EML_MAX_EPS];
+  __shared__ int n_eps_l;
+  const ScanHead head = schedule_scan_begin<1024, 2>(x, y, 1, n, diameter, range_dev);
+  device_schedule<1024, true, 2>(head, x, y, 1, n, blur, log_blur, log_scaling, p, diameter, 0.0, eps_l, lam_l, &n_eps_l,
+                                 eps_out, n_eps_out, diameter_out, nullptr, range_dev, dim);
+  for (int k = n_eps_l + (int)threadIdx.x; k < EML_MAX_EPS; k += 1024) eps_out[k] = 0.f;
+}
+
+// Weight gradients of the loss (sinkhorn_divergence.py:65-69; the weights reach the loop only through detached log-weights,
+// :102-107): d loss_b / d alpha_i = (b_x - a_x)_i, d loss_b / d beta_j = (a_y - b_y)_j, times gloss[b].
+__global__ __launch_bounds__(256) void sinkhorn_bwd_weights_kernel(const float* __restrict__ gloss,
+                                                                   const float* __restrict__ work,
+                                                                   float* __restrict__ galpha, float* __restrict__ gbeta,
+                                                                   int B, int N) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, plane = (size_t)B * N;
+  if (idx >= plane) return;
+  const float g = gloss[idx / N];
+  if (galpha) galpha[idx] = g * (work[3 * plane + idx] - work[idx]);
+  if (gbeta) gbeta[idx] = g * (work[2 * plane + idx] - work[plane + idx]);
 }
 
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ gloss,
@@ -1066,12 +1369,12 @@ void launch_tiled(const float* x, const float* y, const float* M, const float* a
     EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<2>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<2>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
                        log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
-                       B, N, only_if);
+                       B, N, only_if, 1);
   } else {
     EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<1>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<1>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
                        log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
-                       B, N, only_if);
+                       B, N, only_if, 1);
   }
 }
 
@@ -1153,7 +1456,7 @@ extern "C" int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const fl
     EML_ENSURE_LDS((&sinkhorn_loop_kernel<true>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_kernel<true>, dim3(2 * B), dim3(1024), lds, (hipStream_t)stream, x, y, M, Mt,
                        alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       rho, lam_out, work, B, N);
+                       rho, lam_out, work, B, N, 1);
   } else if (N <= 512 && (N & 63) == 0 && N >= 192 && !(flags & EML_SINKHORN_NO_SPLIT) &&
              (split_s = split_slices(B, N, flags, (hipStream_t)stream)) > 0) {
     // small batch: the rows of every problem pair split over S workgroups (one per CU, all resident), duals exchanged
@@ -1194,12 +1497,12 @@ extern "C" int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const fl
     EML_ENSURE_LDS((&sinkhorn_loop_kernel<false>), lds);
     hipLaunchKernelGGL(sinkhorn_loop_kernel<false>, dim3(2 * B), dim3(512), lds, (hipStream_t)stream, x, y, M, Mt,
                        alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       rho, lam_out, work, B, N);
+                       rho, lam_out, work, B, N, 1);
   }
   int rc = eml::check_launch("eml_sinkhorn_fwd_f32(loop)");
   if (rc) return rc;
-  hipLaunchKernelGGL(sinkhorn_finish_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, work, alpha, beta, loss,
-                     gx, gy, B, N);
+  hipLaunchKernelGGL(sinkhorn_finish_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, work, alpha, beta, loss,
+                     gx, gy, B, N, 1);
   return eml::check_launch("eml_sinkhorn_fwd_f32(finish)");
 }
 
@@ -1211,4 +1514,116 @@ extern "C" int eml_sinkhorn_bwd_f32(const float* gloss, const float* gunit, floa
   hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      gloss, gunit, gout, B, N);
   return eml::check_launch("eml_sinkhorn_bwd_f32");
+}
+
+// ---- D-dimensional points (SamplesLoss on (B,N,D) samples, 1 <= D <= EML_SINKHORN_MAX_DIM).  D = 1 forwards to the
+// entries above unchanged.  D > 1 runs the loop kernels instantiated for kD = 2, 4 or 8 components (the smallest that
+// holds D; the components past D are zero and add nothing); the split kernel is not instantiated for it: small batches at
+// 192 <= N <= 512 take the tiled kernel.
+extern "C" size_t eml_sinkhorn_dim_work_floats(int B, int N, int D) {
+  if (B < 0 || N < 1 || D < 1 || D > EML_SINKHORN_MAX_DIM) return 0;
+  if (D == 1) return eml_sinkhorn_work_floats(B, N);
+  return (size_t)(4 + 4 * D) * B * N;   // (4,B,N) duals + (4,B,N,D) expectation rows
+}
+
+extern "C" int eml_sinkhorn_schedule_dim_f32(const float* x, const float* y, long n, int D, double blur, double scaling,
+                                             int p, double diameter, const float* range_lo_hi, float* eps_out,
+                                             int* n_eps_out, float* diameter_out, eml_stream_t stream) {
+  if (D < 1 || D > EML_SINKHORN_MAX_DIM)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: need 1 <= D <= %d (got %d)", EML_SINKHORN_MAX_DIM, D);
+  if (D == 1)
+    return eml_sinkhorn_schedule_f32(x, y, n, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
+                                     stream);
+  if (!eps_out || !n_eps_out || !diameter_out) return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: null output");
+  if (diameter <= 0.0 && (!x || !y || n < 1 || n > (long)INT32_MAX / EML_SINKHORN_MAX_DIM))
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: need x, y, 1<=n<2^28 when diameter is not given");
+  if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: need blur>0, 0<scaling<1, p>=1");
+  hipLaunchKernelGGL(schedule_dim_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, y, (int)std::max(n, 1L), D, blur,
+                     std::log(blur), std::log(scaling), p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out);
+  return eml::check_launch("eml_sinkhorn_schedule_dim_f32");
+}
+
+namespace {
+template <int kD>
+int launch_loop_dim(const float* x, const float* y, const float* M, const float* Mt, const float* alpha,
+                    const float* beta, double blur, double log_blur, double log_scaling, int p, double diameter,
+                    const float* range_lo_hi, float* eps_out, int* n_eps_out, float* diameter_out, double rho,
+                    float* lam_out, float* work, int B, int N, int D, hipStream_t stream) {
+  const int NP = round_up4(N) + kJPT;
+  if (N <= 4 * kCJ) {   // registers: pts [2][kD][NP] + nrm ahead of the D = 1 carve-up, then the chord matrix
+    const size_t lds = (size_t)((kSmemVecs + 2 * kD) * NP + N * (round_up4(N) + 4) + kJPT) * sizeof(float);
+    EML_ENSURE_LDS((&sinkhorn_loop_kernel<true, kD>), lds);
+    hipLaunchKernelGGL((sinkhorn_loop_kernel<true, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, Mt, alpha, beta,
+                       blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out,
+                       work, B, N, D);
+  } else if (N <= 512 && (N & 3) == 0) {   // LDS tiles (also the small batches the split kernel takes at D = 1)
+    const int lpr = N <= 256 ? 2 : 1;
+    const size_t lds = (size_t)((8 + 2 * kD) * NP + 2 * (512 / lpr) * (16 * lpr + 4)) * sizeof(float);
+    if (lpr == 2) {
+      EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<2, kD>), lds);
+      hipLaunchKernelGGL((sinkhorn_loop_tiled_kernel<2, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta,
+                         blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho,
+                         lam_out, work, B, N, nullptr, D);
+    } else {
+      EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<1, kD>), lds);
+      hipLaunchKernelGGL((sinkhorn_loop_tiled_kernel<1, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta,
+                         blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho,
+                         lam_out, work, B, N, nullptr, D);
+    }
+  } else {   // streaming: the same LDS as D = 1 (the norms take the points' place)
+    const size_t lds = (size_t)(kSmemVecs * NP) * sizeof(float);
+    EML_ENSURE_LDS((&sinkhorn_loop_kernel<false, kD>), lds);
+    hipLaunchKernelGGL((sinkhorn_loop_kernel<false, kD>), dim3(2 * B), dim3(512), lds, stream, x, y, M, Mt, alpha, beta,
+                       blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out,
+                       work, B, N, D);
+  }
+  return eml::check_launch("eml_sinkhorn_fwd_dim_f32(loop)");
+}
+}  // namespace
+
+extern "C" int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const float* M, const float* Mt,
+                                        const float* alpha, const float* beta, double blur, double scaling, int p,
+                                        double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                                        float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                                        int D, int flags, double rho, float* lam_out, eml_stream_t stream) {
+  if (D < 1 || D > EML_SINKHORN_MAX_DIM)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need 1 <= D <= %d (got %d)", EML_SINKHORN_MAX_DIM, D);
+  if (D == 1)
+    return eml_sinkhorn_fwd_rho_f32(x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
+                                    diameter_out, loss, gx, gy, work, B, N, flags, rho, lam_out, stream);
+  if (std::isnan(rho)) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: rho is NaN");
+  if (!x || !y || !M || !Mt || !loss || !work) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: null pointer");
+  if (flags & ~(EML_SINKHORN_NO_SPLIT | EML_SINKHORN_FORCE_SPLIT | EML_SINKHORN_TEST_STALL))
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: unknown flags 0x%x", flags);
+  if (B < 0 || N < 1 || N > 2048) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need 1<=N<=2048 (got %d)", N);
+  if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need blur>0, 0<scaling<1, p>=1");
+  if (B == 0) return EML_OK;
+  const double log_blur = std::log(blur), log_scaling = std::log(scaling);
+  const hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (D <= 2)
+    rc = launch_loop_dim<2>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
+                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
+  else if (D <= 4)
+    rc = launch_loop_dim<4>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
+                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
+  else
+    rc = launch_loop_dim<8>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
+                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(sinkhorn_finish_kernel<true>, dim3(B), dim3(256), 0, s, work, alpha, beta, loss, gx, gy, B, N, D);
+  return eml::check_launch("eml_sinkhorn_fwd_dim_f32(finish)");
+}
+
+extern "C" int eml_sinkhorn_bwd_weights_f32(const float* gloss, const float* work, float* galpha, float* gbeta, int B,
+                                            int N, eml_stream_t stream) {
+  if (!gloss || !work || (!galpha && !gbeta) || B < 0 || N < 1)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_bwd_weights_f32: bad arguments");
+  if (B == 0) return EML_OK;
+  const size_t total = (size_t)B * N;
+  hipLaunchKernelGGL(sinkhorn_bwd_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     gloss, work, galpha, gbeta, B, N);
+  return eml::check_launch("eml_sinkhorn_bwd_weights_f32");
 }

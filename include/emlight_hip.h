@@ -174,6 +174,41 @@ int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const float* M, con
 int eml_sinkhorn_bwd_f32(const float* gloss, const float* gunit, float* gout, int B, int N,
                          eml_stream_t stream);
 
+/* D-dimensional samples (ABI 31): SamplesLoss.forward on x, y of shape (B,N,D), the reference's general case
+ * (geomloss/samples_loss.py:35-46, 79-92).  The cost is C_ij = .5*(.1*(|x_i|^2 - 2 x_i.y_j + |y_j|^2) + M_ij)
+ * (utils.py:85-99) and the diameter ||max - min||_2 over the per-component ranges of x U y (sinkhorn_divergence.py:9-18;
+ * the f32 component ranges squared and summed in f64).
+ *   D             1 <= D <= EML_SINKHORN_MAX_DIM; D = 1 forwards to eml_sinkhorn_fwd_rho_f32 with the same arguments
+ *   x, y          (B,N,D) points; alpha, beta (B,N) or NULL, as above
+ *   range_lo_hi   (2*D), device, or NULL: the D component minima, then the D maxima, of the other ranks' shards
+ *   gx, gy        (B,N,D) or NULL
+ *   work          eml_sinkhorn_dim_work_floats(B,N,D) floats; the first (4,B,N) hold the final duals, as above
+ * Every other argument is as eml_sinkhorn_fwd_rho_f32.  D > 1 never takes the split kernel (the small batches it would
+ * take run the tiled kernel; EML_SINKHORN_NO_SPLIT / FORCE_SPLIT / TEST_STALL are accepted and have no effect) and has
+ * no status word.  eml_sinkhorn_dim_work_floats returns 0 for arguments out of range. */
+#define EML_SINKHORN_MAX_DIM 8
+size_t eml_sinkhorn_dim_work_floats(int B, int N, int D);
+int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const float* M, const float* Mt,
+                             const float* alpha, const float* beta, double blur, double scaling, int p,
+                             double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                             float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                             int D, int flags, double rho, float* lam_out, eml_stream_t stream);
+
+/* eml_sinkhorn_schedule_f32 over n D-dimensional points (x, y: (n,D)): the diameter of eml_sinkhorn_fwd_dim_f32
+ * (sinkhorn_divergence.py:9-18, max_diameter) and the same f64 schedule (:21-25); range_lo_hi as there (2*D floats).
+ * D = 1 forwards to eml_sinkhorn_schedule_f32. */
+int eml_sinkhorn_schedule_dim_f32(const float* x, const float* y, long n, int D, double blur, double scaling, int p,
+                                  double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                                  float* diameter_out, eml_stream_t stream);
+
+/* Gradients of the loss with respect to the weights, from the duals a call above left in work[0 : 4*B*N]:
+ * galpha[b,i] = gloss[b] * (b_x - a_x)[b,i],  gbeta[b,j] = gloss[b] * (a_y - b_y)[b,j]  -- the autograd backward of
+ * <alpha,b_x-a_x> + <beta,a_y-b_y> (sinkhorn_divergence.py:65-69), the weights entering the loop only through detached
+ * log-weights (:47-50, 102-107).  The same for any D and any rho (the fork's loss ignores rho).  Either output may be
+ * NULL, not both. */
+int eml_sinkhorn_bwd_weights_f32(const float* gloss, const float* work, float* galpha, float* gbeta, int B, int N,
+                                 eml_stream_t stream);
+
 
 /* ---------------------------------------------------------------- DenseNet-BC encoder, forward
  * All activations are pixel-major (NHWC) f32: a dense block is ONE buffer X[P][ld] whose channel

@@ -8,6 +8,9 @@ windows of `--reps` calls.  Shapes: cfg2 (B=64, N=128, the register-resident ker
 split kernel), blur .05, the inputs of bench.py's Sinkhorn leg.
 
     python tools/bench_sinkhorn.py [--reach .1] [--reps 200] [--windows 7] [--out FILE.json]
+
+``--dim``: instead of balanced vs damped, balanced calls on (B, N, D) samples for D in {1, 2, 4, 8} (eml_sinkhorn_fwd_dim_f32
+for D > 1), alternating window by window the same way.
 """
 import argparse
 import json
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dim", action="store_true", help="time D = 1, 2, 4, 8 samples instead of balanced vs damped")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sinkhorn.py needs the MI355X")
@@ -41,11 +45,22 @@ def main():
         x = torch.softmax(torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
         y = torch.softmax(3 * torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
         calls = {}
-        for label, reach in (("balanced", None), ("reach", a.reach)):
-            crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, reach=reach, anchors=N)
-            out = sinkhorn_outputs(B, N, dev, True, True)
-            calls[label] = (lambda crit=crit, out=out: crit.forward_raw(x, y, out=out))
-        n_eps = int(calls["balanced"]()["n_eps"].item())
+        if a.dim:
+            crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, anchors=N)
+            for D in (1, 2, 4, 8):
+                # component 0 is the 1-D input; the others are further draws of the same recipe
+                xd = torch.cat([x] + [torch.softmax(torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
+                                      for _ in range(D - 1)], 2).contiguous()
+                yd = torch.cat([y] + [torch.softmax(3 * torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
+                                      for _ in range(D - 1)], 2).contiguous()
+                out = sinkhorn_outputs(B, N, dev, True, True, D=D)
+                calls["D%d" % D] = (lambda xd=xd, yd=yd, out=out: crit.forward_raw(xd, yd, out=out))
+        else:
+            for label, reach in (("balanced", None), ("reach", a.reach)):
+                crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, reach=reach, anchors=N)
+                out = sinkhorn_outputs(B, N, dev, True, True)
+                calls[label] = (lambda crit=crit, out=out: crit.forward_raw(x, y, out=out))
+        n_eps = int(next(iter(calls.values()))()["n_eps"].item())
         for fn in calls.values():
             for _ in range(20):
                 fn()
@@ -60,11 +75,17 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 us[k].append(1e3 * e0.elapsed_time(e1) / a.reps)
-        row = {"shape": name, "B": B, "N": N, "n_eps": n_eps, "reach": a.reach}
+        row = {"shape": name, "B": B, "N": N, "n_eps": n_eps}
+        if not a.dim:
+            row["reach"] = a.reach
         for k, v in us.items():
             row[k + "_us"] = round(float(np.median(v)), 2)
             row[k + "_us_min_max"] = [round(float(min(v)), 2), round(float(max(v)), 2)]
-        row["reach_over_balanced"] = round(row["reach_us"] / row["balanced_us"], 4)
+        if a.dim:
+            for D in (2, 4, 8):
+                row["D%d_over_D1" % D] = round(row["D%d_us" % D] / row["D1_us"], 4)
+        else:
+            row["reach_over_balanced"] = round(row["reach_us"] / row["balanced_us"], 4)
         rows.append(row)
         print(json.dumps(row))
     if a.out:
