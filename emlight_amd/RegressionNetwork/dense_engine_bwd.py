@@ -52,6 +52,11 @@ def _masked_stream(dev, n_cu, keep):
 
 
 class _BwdBuffers:
+    def gf12(self, r):
+        if self.GF12[r] is None:
+            self.GF12[r] = self._gf12_new()
+        return self.GF12[r]
+
     def __init__(self, enc, ws, dev):
         f32 = dict(dtype=torch.float32, device=dev)
         self.G = [torch.zeros(blk["P"], blk["ld"], **f32) for blk in ws.blocks]
@@ -61,7 +66,10 @@ class _BwdBuffers:
         # finished gradient of a layer's 12 output channels (compact); a ring, so that the conv3x3 weight gradient of
         # layer l may still be reading slot l % R on the side stream while the main stream is R - 1 layers further
         self.ring = max(1, int(os.environ.get("EML_WGRAD_RING", 4))) if enc.overlap_wgrad(dev) else 1
-        self.GF12 = [torch.empty(maxP, 12, **f32) for _ in range(self.ring)]
+        # Only a SEPARATE weight-gradient launch reads it: the fused conv3x3 backward (the default) gets NULL and stores
+        # nothing, so the slots are allocated on first use (gf12) -- EML_C3_GF=1 hands the buffer over as before (A/B)
+        self.GF12 = [None] * self.ring
+        self._gf12_new = lambda: torch.empty(maxP, 12, **f32)
         self.N12 = torch.empty(maxP, 12, **f32)     # narrow pass: finished gradient of the lower layer's 12 channels
         # the two-layer data-gradient pass's top 24 channels (the next pair's output channels) as two compact tensors: their
         # readers then fetch 48 bytes per pixel instead of one or two 128-byte lines of a wide G row (EML_DGRAD_TOP=0: A/B)
@@ -181,6 +189,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
     # EML_DGAMMA_DIRECT=never exists for A/B timing only.
     direct = knob_choice("EML_DGAMMA_DIRECT", "always", ("always", "never")) != "never"
     c3_fold = knob_flag("EML_C3_FOLD", True)   # read once, not per layer
+    c3_gf = knob_flag("EML_C3_GF", False)      # the fused conv3x3 backward also stores the compact GF12 nobody reads (A/B)
     bw.any_ill.zero_()
 
     def dgamma_direct(blk, X_ld, Pin, Hin, Win, pool, DY, ld_dy, Zr, ld_z, co, Cout, conv, Cin, scale1, shift1, cond, bn):
@@ -263,7 +272,8 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
             Lm = getattr(mod, "denselayer%d" % (l + 1))
             cin, kp, z, dz = lay["Cin"], lay["Kp"], blk["Z"][l], bw.DZ[slot]
             # the gradient of this layer's 12 output channels is complete: its deferred BN1 affine (sB, sC) is
-            # applied inside the conv3x3 dgrad's tile staging, which also leaves the finished gradient in GF12
+            # applied inside the conv3x3 dgrad's tile staging; the unfused data entry also leaves the finished gradient in
+            # GF12 for the separate weight-gradient launch (the fused entry forms dW2 itself and gets no GF)
             gsrc = (p(bw.N12), 12, 0) if n12 else (p(top2[1]), 12, 0) if top else (p(Gbuf), ld, cin)
             r = ring[0] = (ring[0] + 1) % bw.ring
             if bw.side is not None and bw.ev_done[r] is not None:
@@ -279,16 +289,16 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
             if fold:
                 fn = "eml_dense_conv3x3_bwd_fused_drop_f32" if drop else "eml_dense_conv3x3_bwd_fused_f32"
                 _lib.check(getattr(L, fn)(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]), p(lay["zistd"]), p(dz), B, Hb, Wb,
-                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.GF12[r]), p(lay["scale2"]),
-                                          p(lay["shift2"]), p(bw.partW), gr(Lm.conv2.weight), *drop, st), fn)
+                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.gf12(r)) if c3_gf else None,
+                                          p(lay["scale2"]), p(lay["shift2"]), p(bw.partW), gr(Lm.conv2.weight), *drop, st), fn)
             else:
                 fn = "eml_dense_conv3x3_bwd_data_drop_f32" if drop else "eml_dense_conv3x3_bwd_data_f32"
                 _lib.check(getattr(L, fn)(*gsrc, p(Lm.conv2.weight), p(z), p(lay["zmean"]), p(lay["zistd"]), p(dz), B, Hb, Wb,
-                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.GF12[r]), *drop, st), fn)
+                                          p(part), G3d, p(blk["X"]), ld, cin, p(sB), p(sC), p(bw.gf12(r)), *drop, st), fn)
             if fold:
                 pass
             elif bw.side is None:
-                _lib.check(L.eml_dense_conv3x3_bwd_weight_f32(p(bw.GF12[r]), 12, 0, p(z), p(lay["scale2"]),
+                _lib.check(L.eml_dense_conv3x3_bwd_weight_f32(p(bw.gf12(r)), 12, 0, p(z), p(lay["scale2"]),
                                                               p(lay["shift2"]), B, Hb, Wb, p(bw.partW),
                                                               gr(Lm.conv2.weight), G3, st),
                            "eml_dense_conv3x3_bwd_weight_f32")
@@ -296,7 +306,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
                 # dW2 feeds nothing downstream: MFMA-bound, nearly HBM-idle -> side stream, next to the HBM-bound 1x1 chain
                 bw.ev_ready[r].record(main)
                 bw.side.wait_event(bw.ev_ready[r])
-                _lib.check(L.eml_dense_conv3x3_bwd_weight_f32(p(bw.GF12[r]), 12, 0, p(z), p(lay["scale2"]),
+                _lib.check(L.eml_dense_conv3x3_bwd_weight_f32(p(bw.gf12(r)), 12, 0, p(z), p(lay["scale2"]),
                                                               p(lay["shift2"]), B, Hb, Wb, p(bw.partW3[r]),
                                                               gr(Lm.conv2.weight), G3s, st_side),
                            "eml_dense_conv3x3_bwd_weight_f32")

@@ -560,7 +560,9 @@ __device__ unsigned long long eml_c3_stamps[8];
 // Needs the fused BN1 affine (X given).  A16: the 12-channel slices of G and X are 16-byte aligned (blocks 1 and 2); otherwise
 // (block 3 of EMLight's encoder starts at channel 150) each staged item is fetched as two 8-byte loads.
 // DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
-template <bool A16, bool DROP = false>
+// STORE_GF: also leave the compact GF (P, 12) of the staged g -- only a SEPARATE conv3x3_bwd_weight launch reads it, so the
+// launcher instantiates <.., false> when the caller passes GF == NULL (the default path: this kernel forms dW2 itself).
+template <bool A16, bool DROP = false, bool STORE_GF = true>
 __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
@@ -630,7 +632,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
       const int gy = ty * kTH - 1 + w_hy[it], gx = tx * kTW - 1 + w_hx[it];
       w_ok[it] = gy >= 0 && gy < H && gx >= 0 && gx < W;
       w_pix[it] = (b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1);
-      w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
+      if constexpr (STORE_GF) w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
     }
     const int gx = tx * kTW - 1 + s_hx;
     s_y0 = ty * kTH - 1;
@@ -663,7 +665,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
     float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
     *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
     *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
-    if (w_own[it]) *reinterpret_cast<float4*>(GF + (size_t)w_pix[it] * 12 + 4 * w_q[it]) = v;
+    if constexpr (STORE_GF)
+      if (w_own[it]) *reinterpret_cast<float4*>(GF + (size_t)w_pix[it] * 12 + 4 * w_q[it]) = v;
   };
   auto z_load = [&](int it) {
     zt[it] = *reinterpret_cast<const float4*>(s_src + (size_t)min(max(s_y0 + it, 0), H - 1) * W * 48);
@@ -874,7 +877,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
 // structure (A: data gradient, barrier, B: weight gradient with the data gradient's epilogue riding on it, barrier) are
 // conv3x3_bwd_fused_kernel's.
 // DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
-template <bool A16, bool DROP = false>
+// STORE_GF: as in conv3x3_bwd_fused_kernel; false (GF == NULL) drops g_store, w_own and the copy of the committed g kept for it.
+template <bool A16, bool DROP = false, bool STORE_GF = true>
 __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
@@ -956,7 +960,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
       const int gy = ty * kTH - 1 + w_hy[it], gx = tx * kTW - 1 + w_hx[it];
       w_ok[it] = gy >= 0 && gy < H && gx >= 0 && gx < W;
       w_pix[it] = (b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1);
-      w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
+      if constexpr (STORE_GF) w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
     }
   };
   auto g_load = [&](int it) {   // unconditional, clamped
@@ -998,9 +1002,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
     *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
     *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
-    gt4[it] = f32x4{v.x, v.y, v.z, v.w};   // (kept for g_store)
+    if constexpr (STORE_GF) gt4[it] = f32x4{v.x, v.y, v.z, v.w};   // (kept for g_store)
   };
   auto g_store = [&](int it) {
+    if constexpr (!STORE_GF) return;
     // 32-bit element offset from the uniform base (P * 12 < 2^31): as a 64-bit per-lane pointer its loop-invariant part was
     // spilled and reloaded (s_waitcnt vmcnt(0)) in front of every store
     if (w_own[it]) *reinterpret_cast<float4*>(GF + ((unsigned)w_pix[it] * 12u + 4u * (unsigned)w_q[it])) = make_float4(gt4[it][0], gt4[it][1], gt4[it][2], gt4[it][3]);
@@ -3154,7 +3159,7 @@ static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, i
                                     int grid, const float* X, int ldx, int cx, const float* sB, const float* sC, float* GF,
                                     const float* scale2, const float* shift2, float* partialW, float* dW2, eml::DropKey dk,
                                     eml_stream_t stream) {
-  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || !X || !sB || !sC || !GF || !scale2 || !shift2 || !partialW ||
+  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || !X || !sB || !sC || !scale2 || !shift2 || !partialW ||
       !dW2 || B < 1 || H < 1 || W < 1 || grid < 1 || cx < 0)
     return eml::fail(EML_EINVAL, "%s: bad arguments", name);
   const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -3168,13 +3173,25 @@ static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, i
 #if EML_C3_WTP
   const size_t lds = (size_t)(2 * kHH * kHW * kPSG + 2 * kTH * kTW * 48 + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);   // 163 392 of 163 840 bytes
   if (a16) {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP>), lds);
-    hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    if (GF) {
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP, true>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    } else {   // nobody reads GF: no store (see STORE_GF)
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP, false>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    }
   } else {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP>), lds);
-    hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                       zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    if (GF) {
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP, true>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    } else {   // nobody reads GF: no store (see STORE_GF)
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP, false>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
+                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    }
   }
   int rc = eml::check_launch(name);
   if (rc) return rc;
@@ -3184,13 +3201,25 @@ static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, i
 #else
   const size_t lds = (size_t)(2 * kHH * kHW * kPSG + kHH * kHW * kPSW + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);
   if (a16) {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP>), lds);
-    hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    if (GF) {
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP, true>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    } else {   // nobody reads GF: no store (see STORE_GF)
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP, false>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    }
   } else {
-    EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP>), lds);
-    hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                       zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    if (GF) {
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP, true>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    } else {   // nobody reads GF: no store (see STORE_GF)
+      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP, false>), lds);
+      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
+                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+    }
   }
   int rc = eml::check_launch(name);
   if (rc) return rc;

@@ -21,6 +21,8 @@
 //   the 9x48x16 weight fragments stay in registers for the whole persistent loop.
 // Batch statistics for train-mode BN are emitted by every producer's epilogue as per-block
 //   f64 partial (sum, sumsq) and finished by bn_prepare -- deterministic, no atomics.
+#include <algorithm>
+
 #include "eml_common.h"
 #include "eml_dropout.h"
 
@@ -317,6 +319,162 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
   __syncthreads();
   for (int e = tid; e < 96; e += 256)
     partials[(size_t)blockIdx.x * 96 + e] = (red[e] + red[96 + e]) + (red[192 + e] + red[288 + e]);
+}
+
+// ------------------------------------------------------------------------------ conv1x1, wide output (transitions)
+// A transition conv has Cout = 108 / 150 / 171 (EMLight): as chunks of 48 output channels through conv1x1_fwd_kernel<false, false>
+// its operand -- the pooled activation A, 1.1 GB at transition 1, far above the Infinity Cache -- is read from HBM once per
+// chunk.  Here one dispatch takes NT 16-channel output tiles = (NT + 2) / 3 chunks: a wave loads its x fragment once per K-step
+// and runs every tile on it; the tiles of the last chunk past Cout (2 of 9 at Cout = 108) are not computed at all.  Everything a
+// result depends on is conv1x1_fwd_kernel's: tile -> workgroup and lane -> (pixel, channel) mapping, K order (an accumulator's
+// MFMAs are independent of the other tiles'), the epilogue's f32 sums over m and f64 accumulation per tile, shuffles and the
+// 4-wave fold, and the partials of chunk c go to partials + c * chunk_stride as [grid][96] -- bit for bit what the chunk loop
+// writes (the never-computed channels' sums are the +0.0 the chunk loop forms from masked zeros).
+// The weights of all chunks sit in LDS (129 KB at Kp = 224 x 3 chunks): one workgroup per CU, one wave per SIMD, 512 registers
+// per lane (accumulators 16 NT, f64 statistics 16 NT).  With a single wave per SIMD nothing else hides a load: x is requested
+// TWO K-steps ahead (a K-step is 16 NT MFMAs, ~0.2 us per tile).
+template <int NT>
+__global__ __launch_bounds__(256, 1) void conv1x1_fwd_wide_kernel(
+    const float* __restrict__ X, int ldx, int P, int Kp, const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ Wp /* the dispatch's first chunk */, float* __restrict__ out /* its first column */, int ldo,
+    int n_valid /* output channels of this dispatch */, double* __restrict__ partials, size_t chunk_stride /* grid * 96 */) {
+  constexpr int NCH = (NT + 2) / 3;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* wl = smem;                       // [NCH][Kp/16][4][48][4]
+  float* sl = wl + (size_t)NCH * Kp * 48; // [Kp]
+  float* tl = sl + Kp;                    // [Kp]
+  double* red = reinterpret_cast<double*>(tl + Kp);  // [NCH][4][48][2]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, kk = lane >> 4;
+
+#pragma unroll 8
+  for (int e = tid; e < NCH * Kp * 12; e += 256)
+    reinterpret_cast<float4*>(wl)[e] = reinterpret_cast<const float4*>(Wp)[e];
+  for (int e = tid; e < Kp; e += 256) {
+    sl[e] = scale[e];
+    tl[e] = shift[e];
+  }
+  for (int e = tid; e < NCH * 4 * 48 * 2; e += 256) red[e] = 0.0;   // (channels of tiles >= NT keep it)
+  __syncthreads();
+
+  double ssum[NT][4], ssq[NT][4];
+#pragma unroll
+  for (int n = 0; n < NT; ++n)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) ssum[n][g] = ssq[n][g] = 0.0;
+  const int nj = Kp >> 4;   // >= 2 (launcher)
+  const int ntiles = (P + 255) >> 8;
+  const bool vec_ok = (ldo & 3) == 0 && (reinterpret_cast<size_t>(out) & 15) == 0;
+  auto row_ptr = [&](int tile, int m) -> const float* {
+    const int pm = min(tile * 256 + wave * 64 + 16 * m + r, P - 1);
+    return X + (size_t)pm * ldx + 4 * kk;
+  };
+  float4 xa[4], xb[4];   // raw x of the next K-step and of the one after it (unconditional loads, clamped rows)
+  int tile = blockIdx.x;
+  if (tile < ntiles) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      xa[m] = *reinterpret_cast<const float4*>(row_ptr(tile, m));
+      xb[m] = *reinterpret_cast<const float4*>(row_ptr(tile, m) + 16);
+    }
+  }
+  for (; tile < ntiles; tile += gridDim.x) {
+    const int p0 = tile * 256 + wave * 64;
+    const float* rp[4];
+    const float* rpn[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      rp[m] = row_ptr(tile, m);
+      rpn[m] = row_ptr(min(tile + (int)gridDim.x, ntiles - 1), m);
+    }
+    f32x4 acc[4][NT];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll 2
+    for (int j = 0; j < nj; ++j) {
+      const float4 s4 = *reinterpret_cast<const float4*>(sl + 16 * j + 4 * kk);
+      const float4 t4 = *reinterpret_cast<const float4*>(tl + 16 * j + 4 * kk);
+      float4 a[4], xc[4];
+      const bool wrap = j + 2 >= nj;  // wave-uniform
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        xc[m] = xa[m];
+        xa[m] = xb[m];
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m)   // K-step nj + i is the next tile's step i
+        xb[m] = *reinterpret_cast<const float4*>(wrap ? rpn[m] + 16 * (j + 2 - nj) : rp[m] + 16 * (j + 2));
+      __builtin_amdgcn_sched_barrier(0);  // the scheduler otherwise sinks these requests below the MFMAs
+#pragma unroll
+      for (int m = 0; m < 4; ++m) a[m] = bn_relu4(xc[m], s4, t4);
+      float4 bw[NT];
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+        bw[n] = *reinterpret_cast<const float4*>(wl + (size_t)(n / 3) * Kp * 48 + ((size_t)(j * 4 + kk) * 48 + 16 * (n % 3) + r) * 4);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int n = 0; n < NT; ++n) acc[m][n] = mfma16(f4c(bw[n], t), f4c(a[m], t), acc[m][n]);
+    }
+    // epilogue: D rows = channels 16n + 4kk + g (n over the dispatch's chunks: column 48 (n / 3) + 16 (n % 3) + ...), column = pixel 16m + r
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const int c4 = 16 * n + 4 * kk;
+      float ls[4] = {0.f, 0.f, 0.f, 0.f}, lq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const int p = p0 + 16 * m + r;
+        const bool pv = p < P;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float v = (pv && c4 + g < n_valid) ? acc[m][n][g] : 0.f;
+          ls[g] += v;
+          lq[g] = fmaf(v, v, lq[g]);
+        }
+        if (pv) {
+          float* dst = out + (size_t)p * ldo + c4;
+          if (vec_ok && c4 + 4 <= n_valid) {
+            *reinterpret_cast<float4*>(dst) = make_float4(acc[m][n][0], acc[m][n][1], acc[m][n][2], acc[m][n][3]);
+          } else {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              if (c4 + g < n_valid) dst[g] = acc[m][n][g];
+          }
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        ssum[n][g] += (double)ls[g];
+        ssq[n][g] += (double)lq[g];
+      }
+    }
+  }
+  // channel statistics: over the 16 pixel lanes r, then the 4 waves; chunk c = n / 3
+#pragma unroll
+  for (int n = 0; n < NT; ++n)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        ssum[n][g] += shfl_xor_d(ssum[n][g], o);
+        ssq[n][g] += shfl_xor_d(ssq[n][g], o);
+      }
+      if (r == 0) {
+        red[(((n / 3) * 4 + wave) * 48 + 16 * (n % 3) + 4 * kk + g) * 2 + 0] = ssum[n][g];
+        red[(((n / 3) * 4 + wave) * 48 + 16 * (n % 3) + 4 * kk + g) * 2 + 1] = ssq[n][g];
+      }
+    }
+  __syncthreads();
+  for (int e = tid; e < NCH * 96; e += 256) {
+    const int c = e / 96, ee = e - 96 * c;
+    const double* rc = red + c * 384;
+    partials[c * chunk_stride + (size_t)blockIdx.x * 96 + ee] = (rc[ee] + rc[96 + ee]) + (rc[192 + ee] + rc[288 + ee]);
+  }
 }
 
 // ------------------------------------------------------------------------------ conv3x3
@@ -1104,7 +1262,48 @@ extern "C" int eml_dense_conv1x1_fwd_f32(const float* X, int ldx, long P, int Hi
   const size_t lds = lds0 + (staged ? stg_bytes : 0);
   if (lds > 160 * 1024) return eml::fail(EML_EINVAL, "eml_dense_conv1x1_fwd_f32: Kp=%d does not fit LDS", Kp);
   const int nchunks = (Cout + 47) / 48;
-  for (int ch = 0; ch < nchunks; ++ch) {
+  // Wide outputs without pool and mask (the transition convs): as many chunks per dispatch as LDS holds the weights of, at
+  // most 3 (conv1x1_fwd_wide_kernel: x is read once per dispatch instead of once per chunk; same bits).  EMLight's transitions:
+  // Cout = 108, Kp = 224 -> 1 dispatch (3 chunks); 150, 304 and 171, 352 -> 2 dispatches of 2 chunks (they were 3 / 4 / 4).
+  // EML_TRANS_ONEPASS=0: the chunk loop (A/B, tests).
+  static const bool onepass_env = [] { const char* v = getenv("EML_TRANS_ONEPASS"); return !(v && v[0] == '0'); }();
+  int per = 1;
+  if (onepass_env && !pool && !relu_mask && nchunks > 1 && Kp >= 32) {
+    const size_t per_chunk = (size_t)Kp * 48 * sizeof(float) + 4 * 48 * 2 * sizeof(double), fixed = (size_t)2 * Kp * sizeof(float);
+    const int nfit = (int)std::min<size_t>(3, (160 * 1024 - fixed) / per_chunk);
+    if (nfit >= 2) {   // even split over the fewest dispatches
+      const int ndisp = (nchunks + nfit - 1) / nfit;
+      per = (nchunks + ndisp - 1) / ndisp;
+    }
+  }
+  int ch = 0;
+  while (per > 1 && nchunks - ch >= 2) {   // (a lone last chunk goes through the loop below)
+    const int take = std::min(per, nchunks - ch);
+    const int nv = std::min(Cout - ch * 48, 48 * take), nt = (nv + 15) / 16;
+    const size_t wlds = (size_t)take * ((size_t)Kp * 48 * sizeof(float) + 4 * 48 * 2 * sizeof(double)) + (size_t)2 * Kp * sizeof(float);
+    const float* wp = Wp + (size_t)ch * Kp * 48;
+    double* pp = partials + (size_t)ch * grid * 96;
+#define EML_FWD_WIDE(NT_)                                                                                                     \
+  case NT_:                                                                                                                   \
+    EML_ENSURE_LDS((&conv1x1_fwd_wide_kernel<NT_>), wlds);                                                                    \
+    hipLaunchKernelGGL((conv1x1_fwd_wide_kernel<NT_>), dim3(grid), dim3(256), wlds, (hipStream_t)stream, X, ldx, (int)P, Kp,  \
+                       scale, shift, wp, out + ch * 48, ldo, nv, pp, (size_t)grid * 96);                                      \
+    break
+    switch (nt) {
+      EML_FWD_WIDE(4);
+      EML_FWD_WIDE(5);
+      EML_FWD_WIDE(6);
+      EML_FWD_WIDE(7);
+      EML_FWD_WIDE(8);
+      EML_FWD_WIDE(9);
+      default: return eml::fail(EML_EINVAL, "eml_dense_conv1x1_fwd_f32: internal: %d output tiles in %d chunks", nt, take);
+    }
+#undef EML_FWD_WIDE
+    int rc = eml::check_launch("eml_dense_conv1x1_fwd_f32(wide)");
+    if (rc) return rc;
+    ch += take;
+  }
+  for (; ch < nchunks; ++ch) {
     const int nv = (Cout - ch * 48 < 48) ? Cout - ch * 48 : 48;
     const float* wp = Wp + (size_t)ch * Kp * 48;
     double* pp = partials + (size_t)ch * grid * 96;

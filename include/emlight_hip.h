@@ -265,6 +265,9 @@ int eml_dense_permute_batch_f32(const eml_permute_desc* descs, int n, eml_stream
  * (DenseNet.py:30-37; Cout = 48) and, with pool != 0, a transition BN -> ReLU -> conv -> avgpool2
  * (DenseNet.py:14-21; the pool is applied to the operand: it commutes with the 1x1 conv).
  * P output pixels; partials [ceil(Cout/48)][grid][48][2].
+ * Cout > 48 with pool == 0 and no relu_mask (the transition convs on the pooled activation): as many 48-channel chunks per
+ * dispatch as LDS holds the weights of (at most 3) instead of one dispatch per chunk -- X is read once per dispatch; out and
+ * partials are bit for bit the chunk loop's (EML_TRANS_ONEPASS=0 restores it; read once per process).
  * relu_mask (may be NULL; dense layers only): the ReLU mask of the BN1 output as bits, for the backward --
  * 64-bit words [ceil(P/256)*16 pixel groups][Kp/16][4]: word (pg, j, t), bit r + 16*q <-> pixel 16*pg + r,
  * channel 16*j + 4*q + t (q < 4, r < 16); P * Kp / 8 bytes rounded up to whole 256-pixel tiles. */
@@ -353,7 +356,11 @@ int eml_dense_conv3x3_bwd_data_f32(const float* G, int ldg, int c0, const float*
  * issue the two launches); offsets that are multiples of 4 get 16-byte staging loads, the others pairs of 8-byte ones.
  * partials / grid as the data gradient's; partialW: grid*21*256 floats of scratch (sized as the weight gradient's
  * 2*grid*27*256 it always fits); dzn, GF and the statistics are what the separate launches return, dW2 agrees with the
- * separate launch to f32 round-off of the summation order. */
+ * separate launch to f32 round-off of the summation order.
+ * GF may be NULL (here and in eml_dense_conv3x3_bwd_fused_drop_f32; what the engine passes): this entry forms dW2 itself and
+ * GF's only reader is the separate weight-gradient launch, so with NULL the kernel stores no GF at all -- 48 bytes per pixel
+ * less written; dzn, the statistics and dW2 are bit for bit what they are with a buffer.  eml_dense_conv3x3_bwd_data_f32 and
+ * its _drop twin keep requiring GF (with X != NULL). */
 int eml_dense_conv3x3_bwd_fused_supported(int ldg, int c0, int ldx, int cx);
 int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
                                     const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
@@ -362,7 +369,8 @@ int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float
                                     const float* shift2, float* partialW, float* dW2, eml_stream_t stream);
 
 /* Backward of the dense layer's dropout (DenseNet.py:50-55 under autograd) inside the two conv3x3 backwards above (with the
- * fused BN1 affine: X, sB, sC, GF required): the staged g = G + sB*x + sC is multiplied by mask/(1 - p), the mask recomputed
+ * fused BN1 affine: X, sB, sC required; GF required by the data entry, optional for the fused one): the staged
+ * g = G + sB*x + sC is multiplied by mask/(1 - p), the mask recomputed
  * from the forward's (seed, layer, p) -- see eml_dense_conv3x3_fwd_drop_f32.  dzn, its partial sums, the compact GF (what
  * eml_dense_conv3x3_bwd_weight_f32 then reads) and the fused dW2 all use the masked g.  Otherwise the arguments of
  * eml_dense_conv3x3_bwd_data_f32 / eml_dense_conv3x3_bwd_fused_f32.  Additions within ABI 31. */
