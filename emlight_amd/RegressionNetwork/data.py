@@ -7,6 +7,10 @@ licence-restricted Laval Indoor EXR crops + pickled GT parameters; that I/O is o
 and value ranges -- from a seeded generator, and ``PickleParameterDataset`` reads the
 reference's on-disk format (``representation/distribution_representation.py:116-119``)
 when a directory of ``*.pickle`` + ``*.npy`` crops is supplied.
+
+``PanoramaDataset`` + ``PanoramaBatcher`` make the same dict from HDR panoramas on the device: a tonemapped
+perspective crop at a chosen (or per-step random) azimuth and the four targets of ``extract_mesh`` scaled by the crop's
+tonemap alpha -- the reference prepares both offline, one fixed view per panorama.
 """
 import glob
 import os
@@ -75,3 +79,78 @@ class PickleParameterDataset(Dataset):
                 "rgb_ratio": torch.as_tensor(p["rgb_ratio"], dtype=torch.float32),
                 "ambient": torch.as_tensor(p["ambient"], dtype=torch.float32) * alpha / (128 * 256),
                 "name": os.path.basename(path)[:-len(".pickle")]}
+
+
+class PanoramaDataset(Dataset):
+    """``<root>/*.npy`` HDR panoramas ``(H, W, 3)`` (equirect, linear radiance), returned as float32 tensors with their
+    names.  EXR input stays out of scope: convert offline."""
+
+    def __init__(self, root):
+        self.items = sorted(glob.glob(os.path.join(root, "*.npy")))
+        if not self.items:
+            raise FileNotFoundError("no *.npy under %s" % root)
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, idx):
+        path = self.items[idx]
+        pano = np.load(path)
+        if pano.ndim != 3 or pano.shape[2] != 3:
+            raise ValueError("%s: expected a (H, W, 3) panorama, got %s" % (path, pano.shape))
+        return {"pano": torch.from_numpy(np.ascontiguousarray(pano, dtype=np.float32)),
+                "name": os.path.basename(path)[:-len(".npy")]}
+
+
+class PanoramaBatcher:
+    """Device panoramas ``(B, H, W, 3)`` -> the training dict of the reference's ``ParameterDataset`` (``data.py:46-84``):
+
+    * ``crop``: ``TonemapHDR(2.4, 50, 0.5)`` (``data.py:43,63``) of the perspective crop at azimuth ``deg`` and field of view
+      ``fov_deg``, ``(B, 3, h, w)``;
+    * ``distribution`` / ``rgb_ratio``: ``extract_mesh(ln=anchors).compute`` of the rotated panorama area-resized to
+      128 x 256; ``intensity * alpha / 500`` and ``ambient * alpha / (128 * 256)`` (``data.py:71,73``), float32;
+    * ``alpha``: the crop's tonemap alpha ``(B,)``.
+
+    ``deg=None`` draws one azimuth in [0, 360) per sample from a seeded generator that lives on the device; a Python
+    number holds for the batch, a ``(B,)`` device tensor gives one per sample (likewise ``fov_deg``).  The call only
+    enqueues work: no ``.item()``, no ``.cpu()``, no pageable copy.  ``mesh``: an ``extract_mesh`` (h=128, w=256) to share."""
+
+    PANO_HW = (128, 256)
+
+    def __init__(self, anchors=96, crop_hw=(192, 256), fov_deg=60.0, device="cuda", seed=1234, mesh=None):
+        from fractions import Fraction
+        from .representation import extract_mesh
+        from .util import TonemapHDR
+        self.crop_h, self.crop_w = int(crop_hw[0]), int(crop_hw[1])
+        fr = Fraction(self.crop_w, self.crop_h)
+        self.aspect = "%d:%d" % (fr.numerator, fr.denominator)
+        if int(self.crop_h * (fr.numerator / fr.denominator)) != self.crop_w:   # the reference's w = int(h * ratio)
+            raise ValueError("crop_hw %s: int(h * ratio) does not give back w" % (tuple(crop_hw),))
+        self.anchors, self.fov_deg, self.device, self.seed = anchors, fov_deg, torch.device(device), seed
+        self.mesh = mesh if mesh is not None else extract_mesh(h=self.PANO_HW[0], w=self.PANO_HW[1], ln=anchors, device=device)
+        self.tone = TonemapHDR(gamma=2.4, percentile=50, max_mapping=0.5)
+        self.generator = None   # made on the device at the first random draw
+
+    def random_deg(self, B):
+        if self.generator is None:
+            self.generator = torch.Generator(device=self.device)
+            self.generator.manual_seed(self.seed)
+        return torch.rand(B, generator=self.generator, device=self.device, dtype=torch.float64) * 360.0
+
+    def __call__(self, panos, deg=None, fov_deg=None):
+        from .util import PanoramaHandler
+        if panos.dim() != 4:
+            raise ValueError("expected panoramas (B, H, W, 3), got %s" % (tuple(panos.shape),))
+        if deg is None:
+            deg = self.random_deg(panos.shape[0])
+        fov = self.fov_deg if fov_deg is None else fov_deg
+        crop = PanoramaHandler.crop_panorama(panos, fov, self.crop_h, self.aspect, deg=deg)
+        crop, alpha = self.tone(crop)
+        small = PanoramaHandler.resize_panorama(panos, (self.PANO_HW[1], self.PANO_HW[0]), deg=deg)
+        para, _ = self.mesh.compute(small)
+        return {"crop": crop,
+                "distribution": para["distribution"].float(),
+                "intensity": (para["intensity"].float() * alpha / 500.0).reshape(-1, 1),
+                "rgb_ratio": para["rgb_ratio"].float(),
+                "ambient": para["ambient"].float() * alpha[:, None] / (128 * 256),
+                "alpha": alpha}

@@ -29,6 +29,7 @@ class extract_mesh:
         self.csr_pix = order.to(torch.int32).contiguous()
         self.csr_ptr = torch.zeros(ln + 1, dtype=torch.int32, device=dev)
         self.csr_ptr[1:] = torch.cumsum(torch.bincount(self.idx.long(), minlength=ln), 0).to(torch.int32)
+        self.lum = torch.tensor([0.3, 0.59, 0.11], dtype=torch.float64, device=dev)   # made once: compute() only enqueues
 
     def compute(self, hdr):
         single = hdr.dim() == 3
@@ -43,8 +44,7 @@ class extract_mesh:
         _lib.check(L.eml_gt_parametrise_f64(p(x), p(self.csr_ptr), p(self.csr_pix), B, H, W, self.ln, p(maxv), p(sums),
                                             p(lit), st), "eml_gt_parametrise_f64")
         anchors, ambient = sums[:, :self.ln], sums[:, self.ln]
-        lum = torch.tensor([0.3, 0.59, 0.11], dtype=torch.float64, device=x.device)
-        energy = anchors @ lum                                                    # :109
+        energy = anchors @ self.lum                                                   # :109
         rgb = anchors.sum(1)                                                      # :111
         intensity = torch.linalg.norm(rgb, dim=1)                                 # :112
         out = {"distribution": energy / energy.sum(1, keepdim=True), "intensity": intensity,

@@ -4,6 +4,7 @@ torchrun-aware, same optimiser, loss weights, print/visualise/checkpoint cadence
 
     python -m emlight_amd.RegressionNetwork.train --synthetic --epochs 1
     torchrun --nproc-per-node 8 -m emlight_amd.RegressionNetwork.train --synthetic
+    python -m emlight_amd.RegressionNetwork.train --pano_dir DIR --fov 60      # crops and targets made on the GPU per step
 """
 import argparse
 import os
@@ -36,9 +37,7 @@ def save_visual(path, crop, pred, gt, ln, tone):
     Image.fromarray(np.hstack((np.array(c), np.array(env))).astype("uint8")).save(path)
 
 
-def main(argv=None):
-    from emlight_amd import _runtime
-    _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train_dir", default=None, help="directory in PickleParameterDataset format")
     ap.add_argument("--synthetic", action="store_true")
@@ -59,7 +58,24 @@ def main(argv=None):
     ap.add_argument("--save_dir", default="./checkpoints")
     ap.add_argument("--summary_dir", default="./summary")
     ap.add_argument("--load", default=None, help="state_dict to resume from (reference .pth files load)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--pano_dir", default=None,
+                    help="directory of *.npy HDR panoramas (H, W, 3): every step crops a fresh random view of each panorama, "
+                         "tonemaps it and derives the targets on the GPU (data.PanoramaBatcher); overrides --train_dir")
+    ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
+    return ap
+
+
+def make_batcher(args, device):
+    """The ``--pano_dir`` path's panorama -> training-batch step; ``None`` on the default paths (which stay as they are)."""
+    if not args.pano_dir:
+        return None
+    return data.PanoramaBatcher(anchors=args.anchors, crop_hw=tuple(args.crop_hw), fov_deg=args.fov, device=device)
+
+
+def main(argv=None):
+    from emlight_amd import _runtime
+    _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
+    args = build_parser().parse_args(argv)
 
     rank, local, world = init_distributed()
     device = "cuda:%d" % local
@@ -70,7 +86,10 @@ def main(argv=None):
         tr.model.load_state_dict(torch.load(args.load, map_location=device))
         if rank == 0:
             print("load trained model")
-    if args.synthetic or not args.train_dir:
+    batcher = make_batcher(args, device)
+    if batcher is not None:
+        ds = data.PanoramaDataset(args.pano_dir)
+    elif args.synthetic or not args.train_dir:
         ds = data.SyntheticParameterDataset(anchors=args.anchors, crop_hw=tuple(args.crop_hw))
     else:
         ds = data.PickleParameterDataset(args.train_dir)
@@ -88,7 +107,10 @@ def main(argv=None):
         if rank == 0:
             print("{} optim: {}".format(epoch, tr.optimizer.param_groups[0]["lr"]))
         for i, para in enumerate(loader):
-            batch = {k: v.to(device, non_blocking=True) for k, v in para.items() if k != "name"}
+            if batcher is not None:
+                batch = batcher(para["pano"].to(device, non_blocking=True))
+            else:
+                batch = {k: v.to(device, non_blocking=True) for k, v in para.items() if k != "name"}
             loss, terms = tr.step(batch)
             if rank == 0 and i % 10 == 0:  # the only host syncs (train.py:106-108)
                 print("epoch {:0>3d} batch {:0>3d}, ".format(epoch, i)

@@ -1,9 +1,13 @@
 """Mirror of the hot-path parts of the reference's ``RegressionNetwork/util.py``.
 
 ``convert_to_panorama`` (reference ``util.py:222-245``) runs as one HIP kernel each way;
-``sphere_points`` (``util.py:286-299``) and ``TonemapHDR`` (``util.py:36-66``) are the
-small host helpers the kept entry points need.  EXR/vtk/cv2 I/O is out of scope.
+``sphere_points`` (``util.py:286-299``) is the small host helper the kept entry points need.
+``PanoramaHandler`` (``util.py:69-185``: crop, rotate, resize) and ``TonemapHDR`` (``util.py:36-66``) run on device
+tensors, batched (csrc/pano_prep.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
+EXR/vtk/cv2 I/O is out of scope.
 """
+import functools
+
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
@@ -131,14 +135,169 @@ def convert_to_panorama(dirs, sizes, colors, pano_hw=(128, 256)):
     return _Rasterise.apply(d, s, c, int(H), int(W))
 
 
+def _per_sample(value, B, name):
+    """A Python number goes by value and holds for the batch; a device tensor ((B,) or 0-d) gives one f64 value per sample.
+    Returns (by-value float, device tensor or None)."""
+    if isinstance(value, torch.Tensor):
+        if not value.is_cuda:
+            raise _lib.EmlightHipError("%s must be a Python number or a tensor on the MI355X (got %s)" % (name, value.device))
+        if value.dim() == 0:
+            value = value.expand(B)
+        if value.shape != (B,):
+            raise ValueError("%s: expected one value per sample, shape (%d,), got %s" % (name, B, tuple(value.shape)))
+        return 0.0, value.to(torch.float64).contiguous()
+    return float(value), None
+
+
+def parse_aspect_ratio(text):
+    """``"a:b"`` -> a / b (``util.py:152-153``); anything else is a ``ValueError``."""
+    try:
+        num, den = [int(x) for x in str(text).split(":")]
+        ratio = num / den
+    except (ValueError, ZeroDivisionError) as e:
+        raise ValueError("crop_image_aspect_ratio must look like '4:3', got %r" % (text,)) from e
+    if not ratio > 0:
+        raise ValueError("crop_image_aspect_ratio must be positive, got %r" % (text,))
+    return ratio
+
+
+@functools.lru_cache(maxsize=64)
+def crop_sample_extent(fov_deg, h, w, ratio):
+    """The range of the crop's sample positions, as fractions of the panorama's width and height:
+    ``(x_min, x_max, y_min, y_max)`` with position = fraction * W (or H), from the formula of ``util.py:157-174`` in
+    float64.  The azimuth depends on the column alone and the elevation is monotonic in the row, so the extremes lie on
+    the crop's border (its corners and edge midpoints); only the border is evaluated."""
+    scl = np.tan(np.deg2rad(fov_deg) / 2)
+    xs, ys = np.linspace(-scl, scl, w), np.linspace(-scl / ratio, scl / ratio, h)
+    bx = np.concatenate([xs, xs, np.full(h, xs[0]), np.full(h, xs[-1])])
+    by = np.concatenate([np.full(w, ys[0]), np.full(w, ys[-1]), ys, ys])
+    r = np.sqrt(by * by + bx * bx + 1)
+    bx, by = bx / r, by / r
+    bz = np.sqrt(1 - by * by - bx * bx)
+    x = (1 + np.arctan2(bx, bz) / np.pi) / 2
+    y = (1 + np.arcsin(by) / (np.pi / 2)) / 2
+    return float(x.min()), float(x.max()), float(y.min()), float(y.max())
+
+
+def _check_crop_inside(fov_deg, h, w, ratio, H, W):
+    """The reference's interpolator raises ``ValueError`` for a sample outside ``[0, H-1] x [0, W-1]``; so does this,
+    on the host, before any launch."""
+    if not 0.0 < fov_deg < 180.0:
+        raise ValueError("fov_deg must lie in (0, 180), got %r" % (fov_deg,))
+    x0, x1, y0, y1 = crop_sample_extent(float(fov_deg), int(h), int(w), float(ratio))
+    if x0 * W < 0 or x1 * W > W - 1 or y0 * H < 0 or y1 * H > H - 1:
+        raise ValueError("One of the requested xi is out of bounds: a %g degree crop of %d x %d samples rows [%.3f, %.3f] "
+                         "and columns [%.3f, %.3f] of a %d x %d panorama" % (fov_deg, h, w, y0 * H, y1 * H, x0 * W, x1 * W, H, W))
+
+
+class PanoramaHandler(object):
+    """The reference's ``PanoramaHandler`` static methods (``util.py:69-185``) on device tensors, one image
+    ``(H, W, 3)`` or a batch ``(B, H, W, 3)``."""
+
+    @staticmethod
+    def _batched(hdr, name, dtypes=(torch.float32,)):
+        if not isinstance(hdr, torch.Tensor) or hdr.dim() not in (3, 4) or hdr.shape[-1] != 3:
+            raise ValueError("%s: expected a (H, W, 3) or (B, H, W, 3) tensor, got %s"
+                             % (name, tuple(getattr(hdr, "shape", ())) or type(hdr)))
+        single = hdr.dim() == 3
+        dtype = hdr.dtype if hdr.dtype in dtypes else dtypes[0]
+        return _lib.require_gpu_tensor(hdr.unsqueeze(0) if single else hdr, name, dtype), single
+
+    @staticmethod
+    def horizontal_rotate_panorama(hdr_img, deg):
+        """``util.py:102-105``: a plain ``torch.roll`` along the width by ``int(deg / 360 * W)`` columns.  ``crop_panorama``
+        and ``resize_panorama`` fold the same shift into their gathers (``deg=``) and need no rolled copy."""
+        return torch.roll(hdr_img, shifts=int(deg / 360.0 * hdr_img.shape[-2]), dims=-2)
+
+    @staticmethod
+    def crop_panorama(hdr_img, fov_deg, crop_image_h=720, crop_image_aspect_ratio="4:3", deg=0.0):
+        """Perspective crop of an equirect panorama (``util.py:147-185``), rotated by ``deg`` first (``:102-105``):
+        ``(B, H, W, 3)`` float32 or uint8 (divided by 255) -> ``(B, 3, h, w)`` float32, channel-first as ``ToTensor``
+        hands it to the network (``data.py:64``).  ``fov_deg`` and ``deg``: a Python number for the whole batch (passed by
+        value; a shared field of view evaluates each pixel's position once for a run of images) or a ``(B,)`` device
+        tensor, one value per sample.  A by-value ``fov_deg`` whose samples leave ``[0, H-1] x [0, W-1]`` raises
+        ``ValueError`` before any launch, like the reference's interpolator; a per-sample tensor cannot be checked
+        without a host synchronisation, there such pixels come out as NaN.  Nothing is clamped."""
+        x, single = PanoramaHandler._batched(hdr_img, "hdr_img", (torch.float32, torch.uint8))
+        ratio = parse_aspect_ratio(crop_image_aspect_ratio)
+        h = int(crop_image_h)
+        w = int(h * ratio)
+        if h < 1 or w < 1:
+            raise ValueError("empty crop: crop_image_h=%r, aspect %r" % (crop_image_h, crop_image_aspect_ratio))
+        B, H, W, _ = x.shape
+        fov, fov_t = _per_sample(fov_deg, B, "fov_deg")
+        dg, deg_t = _per_sample(deg, B, "deg")
+        if fov_t is None:
+            _check_crop_inside(fov, h, w, ratio, H, W)
+        out = torch.empty(B, 3, h, w, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().eml_pano_crop_f32(_lib.ptr(x), 1 if x.dtype == torch.uint8 else 0, B, H, W, h, w, ratio, fov,
+                                                _lib.ptr(fov_t), dg, _lib.ptr(deg_t), _lib.ptr(out), _lib.current_stream()),
+                   "eml_pano_crop_f32")
+        return out[0] if single else out
+
+    @staticmethod
+    def resize_panorama(hdr_img, new_shape, deg=0.0):
+        """``util.py:139-144`` with the rotation folded in: ``new_shape`` is ``(w, h)`` or an int ``h`` meaning
+        ``(2h, h)``; ``(B, H, W, 3)`` float32 -> ``(B, h, w, 3)``.  The operation is DEFINED here as the box mean: output
+        pixel ``(i, j)`` is the mean of its ``(H/h) x (W/w)`` box of source pixels, summed in float64 in a fixed order.
+        Only integer factors are accepted (``ValueError`` otherwise).  The reference calls ``cv2.resize(...,
+        INTER_AREA)``; cv2 was not available to compare against, so parity with it is neither tested nor claimed."""
+        x, single = PanoramaHandler._batched(hdr_img, "hdr_img")
+        if isinstance(new_shape, tuple) and len(new_shape) == 2:
+            w, h = int(new_shape[0]), int(new_shape[1])
+        elif isinstance(new_shape, int):
+            w, h = 2 * new_shape, new_shape
+        else:
+            raise ValueError("new_shape must be (w, h) or an int h, got %r" % (new_shape,))
+        B, H, W, _ = x.shape
+        if h < 1 or w < 1 or H % h != 0 or W % w != 0:
+            raise ValueError("resize_panorama takes integer factors only: %d x %d -> %d x %d" % (H, W, h, w))
+        dg, deg_t = _per_sample(deg, B, "deg")
+        out = torch.empty(B, h, w, 3, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().eml_pano_resize_area_f32(_lib.ptr(x), B, H, W, h, w, dg, _lib.ptr(deg_t), _lib.ptr(out),
+                                                       _lib.current_stream()), "eml_pano_resize_area_f32")
+        return out[0] if single else out
+
+
+def tonemap_raw(img, gamma=2.4, percentile=50, max_mapping=0.5, clip=True, alpha=None, use_gamma=True, apply=True):
+    """``eml_tonemap_f32`` on a batch ``(B, ...)`` of images, with its raw per-image outputs: dict of ``out`` (like ``img``;
+    ``None`` without ``apply``), ``P`` = img^(1/gamma), ``n`` (B,) int32 = number of positive values, ``lo`` / ``hi`` (B,) =
+    the order statistics at floor / floor + 1 of the virtual index ``(n - 1) * percentile / 100``, ``r`` (B,) the
+    percentile, ``alpha`` (B,).  ``alpha``: a Python number or a (B,) device tensor to use instead of the computed one."""
+    x = _lib.require_gpu_tensor(img, "img")
+    B = x.shape[0]
+    n = x[0].numel() if B else 1
+    if isinstance(alpha, torch.Tensor):
+        alpha_t = _lib.require_gpu_tensor(alpha.expand(B) if alpha.dim() == 0 else alpha, "alpha")
+        if alpha_t.shape != (B,):
+            raise ValueError("alpha: expected shape (%d,), got %s" % (B, tuple(alpha_t.shape)))
+    elif alpha is not None:
+        alpha_t = torch.full((B,), float(alpha), dtype=torch.float32, device=x.device)
+    else:
+        alpha_t = None
+    L = _lib.lib()
+    P = torch.empty_like(x)
+    out = torch.empty_like(x) if apply else None
+    cnt = torch.empty(B, dtype=torch.int32, device=x.device)
+    stats = torch.empty(B, 4, dtype=torch.float32, device=x.device)
+    work = torch.empty(max(1, L.eml_tonemap_work_floats(B)), dtype=torch.int32, device=x.device)
+    _lib.check(L.eml_tonemap_f32(_lib.ptr(x), B, n, 1 if use_gamma else 0, float(gamma) if use_gamma else 1.0, float(percentile),
+                                 float(max_mapping), _lib.ptr(alpha_t), 1 if clip else 0, _lib.ptr(P), _lib.ptr(out),
+                                 _lib.ptr(cnt), _lib.ptr(stats), _lib.ptr(work), _lib.current_stream()), "eml_tonemap_f32")
+    return {"out": out, "P": P, "n": cnt, "lo": stats[:, 0], "hi": stats[:, 1], "r": stats[:, 2], "alpha": stats[:, 3]}
+
+
 class TonemapHDR(object):
     """Global tonemap: alpha maps the ``percentile`` of I^(1/gamma) to ``max_mapping``
-    (reference ``util.py:36-66``); numpy, host side (visualisation only)."""
+    (reference ``util.py:36-66``).  numpy input: numpy, host side (visualisation).  A device tensor ``(3, h, w)`` or a
+    batch ``(B, 3, h, w)``: the HIP kernels, one alpha per image, no host round trip; returns ``(tensor, alpha tensor)``."""
 
     def __init__(self, gamma=2.4, percentile=50, max_mapping=0.5):
         self.gamma, self.percentile, self.max_mapping = gamma, percentile, max_mapping
 
     def __call__(self, numpy_img, clip=True, alpha=None, gamma=True):
+        if isinstance(numpy_img, torch.Tensor):
+            return self._tensor(numpy_img, clip, alpha, gamma)
         img = np.power(numpy_img, 1 / self.gamma) if gamma else numpy_img
         pos = img > 0
         ref = np.percentile(img[pos], self.percentile) if pos.any() else np.percentile(img, self.percentile)
@@ -148,3 +307,11 @@ class TonemapHDR(object):
         if clip:
             out = np.clip(out, 0, 1)
         return out.astype("float32"), alpha
+
+    def _tensor(self, img, clip, alpha, gamma):
+        if img.dim() not in (3, 4):
+            raise ValueError("expected a (3, h, w) image or a (B, 3, h, w) batch, got %s" % (tuple(img.shape),))
+        single = img.dim() == 3
+        raw = tonemap_raw(img.unsqueeze(0) if single else img, self.gamma, self.percentile, self.max_mapping, clip=clip,
+                          alpha=alpha, use_gamma=bool(gamma))
+        return (raw["out"][0], raw["alpha"][0]) if single else (raw["out"], raw["alpha"])

@@ -58,6 +58,13 @@ SIGNATURES = {
     # ground-truth parametrisation
     "eml_gt_anchor_index_i32": (_int, [_f32p, _int, _int, _int, _i32p, _stream]),
     "eml_gt_parametrise_f64": (_int, [_f32p, _i32p, _i32p, _int, _int, _int, _int, _f32p, _f32p, _f32p, _stream]),
+    # HDR panorama -> training batch: crop with folded rotation, area resize, tonemap (radix select)
+    "eml_pano_crop_f32": (_int, [ctypes.c_void_p, _int, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double, _f64p,
+                                 ctypes.c_double, _f64p, _f32p, _stream]),
+    "eml_pano_resize_area_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_double, _f64p, _f32p, _stream]),
+    "eml_tonemap_work_floats": (ctypes.c_size_t, [_int]),
+    "eml_tonemap_f32": (_int, [_f32p, _int, ctypes.c_long, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f32p,
+                               _int, _f32p, _f32p, _i32p, _f32p, ctypes.c_void_p, _stream]),
     # GenProjector SphereConv2D
     "eml_sphere_tap_table_f32": (_int, [_f32p, _int, _int, _int, _int, _i32p, _f32p, _stream]),
     "eml_sphere_im2col_f32": (_int, [_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),

@@ -851,6 +851,39 @@ int eml_gt_anchor_index_i32(const double* anchors, int N, int H, int W, int* idx
 int eml_gt_parametrise_f64(const float* hdr, const int* csr_ptr, const int* csr_pix, int B, int H, int W,
                            int N, double* maxv, double* sums, unsigned char* map, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- HDR panorama -> training batch (data preparation)
+ * RegressionNetwork/util.py:147-185 (`PanoramaHandler.crop_panorama`) fused with :102-105
+ * (`horizontal_rotate_panorama`).  pano (B,H,W,3) f32, or u8 (is_u8 != 0: divided by 255, :149-150) -> out (B,3,h,w)
+ * f32: the bilinear sample (scipy's RegularGridInterpolator, linear) at the reference's f64 position of every pixel of
+ * the tangent-plane grid of a `fov` degree view with aspect `ratio` = w / h.  The rotation is folded into the gather:
+ * source column (j - shift) mod W, shift = int(deg / 360 * W) truncated toward zero.  fov_dev / deg_dev: (B) f64 device
+ * arrays, one value per sample, or NULL: then fov_deg / deg (by value) hold for the batch, and with a shared fov every
+ * thread evaluates its position once for a run of images.  A position outside [0,H-1] x [0,W-1] -- where the reference
+ * raises; the caller checks a by-value fov on the host -- gives NaN: nothing is clamped.
+ * The four entry points of this section are additions within ABI 31 (no existing signature changed; the binding refuses a
+ * library without them by name). */
+int eml_pano_crop_f32(const void* pano, int is_u8, int B, int H, int W, int h, int w, double ratio, double fov_deg,
+                      const double* fov_dev, double deg, const double* deg_dev, float* out, eml_stream_t stream);
+
+/* RegressionNetwork/util.py:139-144 (`resize_panorama`) as the box mean over integer factors (H % h == 0, W % w == 0,
+ * else EML_EINVAL), with the same folded rotation: pano (B,H,W,3) f32 -> out (B,h,w,3) f32, each output the mean of
+ * its (H/h) x (W/w) source box, summed in f64 in a fixed order (run-to-run exact). */
+int eml_pano_resize_area_f32(const float* pano, int B, int H, int W, int h, int w, double deg, const double* deg_dev,
+                             float* out, eml_stream_t stream);
+
+/* RegressionNetwork/util.py:36-66 (`TonemapHDR.__call__`) per image of a batch: img (B, n) f32 (n = 3*h*w values per
+ * image) -> P = img^(1/gamma) with the exponent rounded to f32 (use_gamma == 0: P = img), r = numpy's linear
+ * `percentile` of the positive values of P, alpha = max_mapping / (r + 1e-10) in f32 unless alpha_in (B) is given,
+ * out = alpha * P clipped to [0,1] when clip (out may be NULL: selection only).  The order statistics are exact (a
+ * three-pass radix select over integer histograms, no sort, bit-reproducible).  Raw outputs per image: n_out (B) i32 =
+ * number of positive values, stats (B,4) f32 = the two order statistics at floor / floor + 1 of the virtual index
+ * f32(n - 1) * (f32(percentile) / f32(100)) -- numpy forms it in the array's type --, r, alpha.  An image without a positive value has n = 0 and r = 0.  P: (B, n) f32, written.
+ * work: eml_tonemap_work_floats(B) 4-byte words of scratch. */
+size_t eml_tonemap_work_floats(int B);
+int eml_tonemap_f32(const float* img, int B, long n, int use_gamma, double gamma, double percentile, double max_mapping,
+                    const float* alpha_in, int clip, float* P, float* out, int* n_out, float* stats, void* work,
+                    eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
