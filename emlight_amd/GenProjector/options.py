@@ -12,7 +12,9 @@ default, so that ``train_laval.sh`` / ``test.sh`` run against this package uncha
   reader and the HTML visualiser are out of scope (the data loader is the caller's); with ``--synthetic`` they
   are accepted and ignored (one line says which), without it a non-default ``--dataset_mode`` is an error that says so.
 
-Options of this build that the reference does not have: ``--synthetic --iters_per_epoch --max_iters`` and the VGG switches.
+Options of this build that the reference does not have: ``--synthetic --iters_per_epoch --max_iters``, the VGG switches and
+``--pano_dir DIR [--fov F]``: batches made on the GPU from a directory of ``*.npy`` HDR panoramas
+(``data.ProjectorPanoramaBatcher``); the dataset / display flags are ignored there as under ``--synthetic``.
 """
 import argparse
 import os
@@ -133,13 +135,13 @@ def resolve_gpu_ids(gpu_ids, world, local_rank=0):
                      % (gpu_ids, len(ids), world))
 
 
-def check_data_flags(args, ap, synthetic, verbose=True):
-    """Dataset / display flags: ignored (and named, once) on the synthetic path, refused otherwise."""
+def check_data_flags(args, ap, synthetic, verbose=True, pano_dir=None):
+    """Dataset / display flags: ignored (and named, once) on the synthetic and the ``--pano_dir`` paths, refused otherwise."""
     given = [k for k in IGNORED_DATA_FLAGS if hasattr(args, k) and getattr(args, k) != ap.get_default(k)]
-    if synthetic:
+    if synthetic or pano_dir:
         if given and verbose:
-            print("GenProjector: --synthetic batches -- these reference dataset / display options are accepted and "
-                  "ignored: %s" % ", ".join("--" + k for k in given))
+            print("GenProjector: %s batches -- these reference dataset / display options are accepted and "
+                  "ignored: %s" % ("--pano_dir" if pano_dir else "--synthetic", ", ".join("--" + k for k in given)))
         return given
     raise SystemExit("GenProjector: the Laval dataset reader (--dataset_mode %s, --dataroot %s) is outside this package "
                      "(SURVEY 8b: the data loader is the caller's): pass --synthetic for the seeded synthetic batches of "
@@ -169,9 +171,18 @@ def network_options(args, is_train=True, **extra):
     return networks.default_options(**kw)
 
 
+def add_pano_options(ap):
+    ap.add_argument("--pano_dir", default=None,
+                    help="directory of *.npy HDR panoramas (H, W, 3): input, crop, warped and map of every batch are made on the "
+                         "GPU from a fresh random view of each panorama (data.ProjectorPanoramaBatcher); wins over --synthetic")
+    ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
+    return ap
+
+
 def train_parser():
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     add_train_options(ap)
+    add_pano_options(ap)
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches (SURVEY 8d) instead of the Laval dataset")
     ap.add_argument("--iters_per_epoch", type=int, default=100, help="synthetic: iterations that make an epoch")
     ap.add_argument("--max_iters", type=int, default=0, help="stop after this many iterations (0: run niter + niter_decay epochs)")
@@ -181,6 +192,7 @@ def train_parser():
 def test_parser():
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     add_test_options(ap)
+    add_pano_options(ap)
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches (SURVEY 8d) instead of the Laval dataset")
     return ap
 

@@ -6,8 +6,10 @@
         --display_freq 1000 --batchSize 16 --niter 100 --niter_decay 100 --gpu_ids 0 --continue_train      # train_laval.sh's flags
     python -m emlight_amd.GenProjector.train --synthetic --continue_train --which_epoch latest     # resume (iter.txt)
     torchrun --nproc-per-node 8 -m emlight_amd.GenProjector.train --synthetic
+    python -m emlight_amd.GenProjector.train --pano_dir DIR --fov 60 --batchSize 8     # batches made on the GPU from *.npy panoramas
 """
 import argparse
+import itertools
 import os
 
 import torch
@@ -27,8 +29,26 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     options.resolve_gpu_ids(args.gpu_ids, options.world_from_env())
     args.ignored_reference_flags = options.check_data_flags(args, ap, args.synthetic,
-                                                            verbose=int(os.environ.get("RANK", "0")) == 0)
+                                                            verbose=int(os.environ.get("RANK", "0")) == 0, pano_dir=args.pano_dir)
     return args
+
+
+def make_pano_loader(args, device, rank, world):
+    """``--pano_dir``: ``(batcher, loader, sampler)`` -- ``PanoramaDataset`` behind the ``DataLoader`` / ``DistributedSampler``
+    arrangement of ``RegressionNetwork/train.py``, and the panorama -> projector-batch step; ``(None, None, None)`` without it."""
+    if not args.pano_dir:
+        return None, None, None
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+    from ..RegressionNetwork.data import PanoramaDataset
+    ds = PanoramaDataset(args.pano_dir)
+    if len(ds) < args.batchSize * world:
+        raise SystemExit("--pano_dir %s holds %d panoramas, fewer than one global batch (%d)"
+                         % (args.pano_dir, len(ds), args.batchSize * world))
+    sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
+    loader = DataLoader(ds, batch_size=args.batchSize, shuffle=sampler is None, sampler=sampler, drop_last=True, num_workers=2,
+                        pin_memory=True)
+    return data.ProjectorPanoramaBatcher(fov_deg=args.fov, device=device, seed=1234 + rank), loader, sampler
 
 
 def main(argv=None):
@@ -47,15 +67,29 @@ def main(argv=None):
     if args.continue_train:
         tr.load(args.which_epoch, save_dir)      # every rank loads the same files: replicas start identical
     global_batch = args.batchSize * world
-    counter = IterationCounter(args.checkpoints_dir, args.name, args.iters_per_epoch * global_batch, global_batch, args.niter,
+    batcher, loader, sampler = make_pano_loader(args, dev, rank, world)
+    # --pano_dir: one epoch is one pass over the directory; synthetic: --iters_per_epoch iterations
+    dataset_size = len(loader.dataset) if loader is not None else args.iters_per_epoch * global_batch
+    counter = IterationCounter(args.checkpoints_dir, args.name, dataset_size, global_batch, args.niter,
                                args.niter_decay, args.continue_train, args.print_freq, args.save_latest_freq,
                                args.save_epoch_freq)
     it = 0
     for epoch in counter.training_epochs():
         counter.record_epoch_start(epoch)
-        for i in range(counter.epoch_iter // global_batch, args.iters_per_epoch):
+        first = counter.epoch_iter // global_batch          # > 0 in the epoch a run resumes in
+        if loader is not None:
+            if sampler is not None:
+                sampler.set_epoch(epoch)
+            feed = enumerate(itertools.islice(loader, first, None), first)
+        else:
+            feed = ((i, None) for i in range(first, args.iters_per_epoch))
+        for i, para in feed:
             counter.record_one_iteration()
-            batch = data.projector_batch(args.batchSize, dev, seed=1234 + rank + 977 * (counter.total_steps_so_far // global_batch))
+            if para is not None:
+                batch = batcher(para["pano"].to(dev, non_blocking=True))
+            else:
+                batch = data.projector_batch(args.batchSize, dev,
+                                             seed=1234 + rank + 977 * (counter.total_steps_so_far // global_batch))
             if i % args.D_steps_per_G == 0:          # train.py:33-37
                 tr.run_generator_one_step(batch)
             tr.run_discriminator_one_step(batch)
@@ -80,6 +114,7 @@ def main(argv=None):
                 counter.record_current_iter()
         if stop:
             break
+    return tr.get_latest_losses()      # the last iteration's loss terms (device tensors), for callers that drive main() themselves
 
 
 if __name__ == "__main__":

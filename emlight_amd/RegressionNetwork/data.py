@@ -137,20 +137,35 @@ class PanoramaBatcher:
             self.generator.manual_seed(self.seed)
         return torch.rand(B, generator=self.generator, device=self.device, dtype=torch.float64) * 360.0
 
-    def __call__(self, panos, deg=None, fov_deg=None):
-        from .util import PanoramaHandler
+    def view(self, panos, deg=None, fov_deg=None):
+        """The batch's ``(deg, fov_deg)``: what was passed, else one drawn azimuth per sample and the constructor's field of
+        view.  ``GenProjector.data.ProjectorPanoramaBatcher`` draws its views through this, so the two agree."""
         if panos.dim() != 4:
             raise ValueError("expected panoramas (B, H, W, 3), got %s" % (tuple(panos.shape),))
         if deg is None:
             deg = self.random_deg(panos.shape[0])
-        fov = self.fov_deg if fov_deg is None else fov_deg
-        crop = PanoramaHandler.crop_panorama(panos, fov, self.crop_h, self.aspect, deg=deg)
-        crop, alpha = self.tone(crop)
-        small = PanoramaHandler.resize_panorama(panos, (self.PANO_HW[1], self.PANO_HW[0]), deg=deg)
-        para, _ = self.mesh.compute(small)
-        return {"crop": crop,
-                "distribution": para["distribution"].float(),
+        return deg, (self.fov_deg if fov_deg is None else fov_deg)
+
+    def crop(self, panos, deg, fov):
+        """The raw (HDR) perspective crop ``(B, 3, h, w)`` of the view."""
+        from .util import PanoramaHandler
+        return PanoramaHandler.crop_panorama(panos, fov, self.crop_h, self.aspect, deg=deg)
+
+    def small(self, panos, deg):
+        """The rotated panorama area-resized to 128 x 256, ``(B, 128, 256, 3)``."""
+        from .util import PanoramaHandler
+        return PanoramaHandler.resize_panorama(panos, (self.PANO_HW[1], self.PANO_HW[0]), deg=deg)
+
+    @staticmethod
+    def targets(para, alpha):
+        """``extract_mesh.compute``'s parameters -> the four float32 regression targets (``data.py:70-73``)."""
+        return {"distribution": para["distribution"].float(),
                 "intensity": (para["intensity"].float() * alpha / 500.0).reshape(-1, 1),
                 "rgb_ratio": para["rgb_ratio"].float(),
-                "ambient": para["ambient"].float() * alpha[:, None] / (128 * 256),
-                "alpha": alpha}
+                "ambient": para["ambient"].float() * alpha[:, None] / (128 * 256)}
+
+    def __call__(self, panos, deg=None, fov_deg=None):
+        deg, fov = self.view(panos, deg, fov_deg)
+        crop, alpha = self.tone(self.crop(panos, deg, fov))
+        para, _ = self.mesh.compute(self.small(panos, deg))
+        return {"crop": crop, **self.targets(para, alpha), "alpha": alpha}

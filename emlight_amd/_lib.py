@@ -65,6 +65,10 @@ SIGNATURES = {
     "eml_tonemap_work_floats": (ctypes.c_size_t, [_int]),
     "eml_tonemap_f32": (_int, [_f32p, _int, ctypes.c_long, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f32p,
                                _int, _f32p, _f32p, _i32p, _f32p, ctypes.c_void_p, _stream]),
+    # projector inputs from a panorama: warped * alpha + light mask, bilinear resize of the (tonemapped) crop
+    "eml_projector_targets_work_floats": (ctypes.c_size_t, [_int, _int, _int]),
+    "eml_projector_targets_f32": (_int, [_f32p, _f32p, _int, _int, _int, _f32p, _f32p, _f32p, _stream]),
+    "eml_resize_bilinear_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, _int, _int, _f32p, _stream]),
     # GenProjector SphereConv2D
     "eml_sphere_tap_table_f32": (_int, [_f32p, _int, _int, _int, _int, _i32p, _f32p, _stream]),
     "eml_sphere_im2col_f32": (_int, [_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),

@@ -21,6 +21,7 @@ all-reduce over RCCL/xGMI) and SPADE's batch norm synchronises its statistics (`
 
     python -m emlight_amd.joint --batch 8 --max_iters 10
     torchrun --nproc-per-node 8 -m emlight_amd.joint --batch 32
+    python -m emlight_amd.joint --pano_dir DIR --fov 60 --batch 8      # crops, targets, warped and map made on the GPU per step
 """
 import argparse
 
@@ -54,7 +55,9 @@ class JointTrainer:
         self.losses = {}
 
     def projector_inputs(self, batch, pred):
-        crop128 = F.interpolate(batch["crop"], size=(128, 128), mode="bilinear", align_corners=False)
+        crop128 = batch.get("crop128")      # ProjectorPanoramaBatcher(regression=True) made it from the tonemap's P and alpha
+        if crop128 is None:
+            crop128 = F.interpolate(batch["crop"], size=(128, 128), mode="bilinear", align_corners=False)
         return {"input": predicted_gaussian_map(pred, self.ln, self.pano_hw), "crop": crop128,
                 "warped": batch["warped"], "map": batch["map"]}
 
@@ -113,9 +116,7 @@ def joint_batch(batch, device, anchors=128, crop_hw=(240, 320), pano_hw=(128, 25
     return p
 
 
-def main(argv=None):
-    from emlight_amd import _runtime
-    _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE configs[3]: 256 over 8 GPUs)")
     ap.add_argument("--anchors", type=int, default=128)
@@ -128,16 +129,55 @@ def main(argv=None):
     ap.add_argument("--ngf", type=int, default=64)
     ap.add_argument("--ndf", type=int, default=64)
     ap.add_argument("--max_iters", type=int, default=100)
+    ap.add_argument("--pano_dir", default=None,
+                    help="directory of *.npy HDR panoramas (H, W, 3): every step crops a fresh random view of each panorama and "
+                         "makes the regression targets and the projector's warped / map on the GPU "
+                         "(GenProjector.data.ProjectorPanoramaBatcher(regression=True)); --max_iters counts its steps")
+    ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
     networks.add_vgg_arguments(ap)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def pano_batches(args, device, rank, world):
+    """``--pano_dir``: an endless stream of joint batches, one pass over the directory after the other, with the
+    ``DataLoader`` / ``DistributedSampler`` arrangement of ``RegressionNetwork/train.py``."""
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+    from .RegressionNetwork.data import PanoramaDataset
+    ds = PanoramaDataset(args.pano_dir)
+    if len(ds) < args.batch * world:
+        raise SystemExit("--pano_dir %s holds %d panoramas, fewer than one global batch (%d)" % (args.pano_dir, len(ds),
+                                                                                                args.batch * world))
+    batcher = projector_data.ProjectorPanoramaBatcher(anchors=args.anchors, crop_hw=tuple(args.crop_hw), fov_deg=args.fov,
+                                                      device=device, seed=1234 + rank, regression=True)
+    sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
+    loader = DataLoader(ds, batch_size=args.batch, shuffle=sampler is None, sampler=sampler, drop_last=True, num_workers=2,
+                        pin_memory=True)
+    epoch = 0
+    while True:
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        for para in loader:
+            yield batcher(para["pano"].to(device, non_blocking=True))
+        epoch += 1
+
+
+def main(argv=None):
+    from emlight_amd import _runtime
+    _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
+    args = build_parser().parse_args(argv)
     rank, local, world = init_distributed()
     dev = "cuda:%d" % local
     tr = JointTrainer(networks.default_options(ngf=args.ngf, ndf=args.ndf, **networks.vgg_options(args, verbose=rank == 0)),
                       anchors=args.anchors,
                       crop_hw=tuple(args.crop_hw), blur=args.blur, device=dev, world=world, reach=args.reach,
                       drop_rate=args.drop_rate)
+    stream = pano_batches(args, dev, rank, world) if args.pano_dir else None
     for it in range(args.max_iters):
-        batch = joint_batch(args.batch, dev, args.anchors, tuple(args.crop_hw), seed=1234 + rank + 977 * it)
+        if stream is not None:
+            batch = next(stream)
+        else:
+            batch = joint_batch(args.batch, dev, args.anchors, tuple(args.crop_hw), seed=1234 + rank + 977 * it)
         losses = tr.step(batch)
         if rank == 0 and it % 10 == 0:   # the only host syncs
             print("iter %d " % it + " ".join("%s: %.4f" % (k, float(v.mean())) for k, v in losses.items()))

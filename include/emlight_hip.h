@@ -884,6 +884,32 @@ int eml_tonemap_f32(const float* img, int B, long n, int use_gamma, double gamma
                     const float* alpha_in, int clip, float* P, float* out, int* n_out, float* stats, void* work,
                     eml_stream_t stream);
 
+/* ---------------------------------------------------------------- projector inputs from a panorama (data preparation)
+ * GenProjector/data.py:73-84: the real panorama times the crop's tonemap alpha and the light mask of its luma.
+ * small (B,h,w,3) f32 pixel-major (what eml_pano_resize_area_f32 writes), alpha (B) f32 on the device or NULL for 1 ->
+ * warped (B,3,h,w) = small[b] * alpha[b], one f32 multiply per value, channel-first (:82-84);
+ * map (B,1,h,w) f32 in {0,1} = luma > thr_b (:75-81), DEFINED in f32 in the reference's association, no contraction:
+ *   luma = (f32(.3) R + f32(.59) G) + f32(.11) B, every product and sum rounded to f32;  thr_b = f32(max_b(luma) * f32(.05)).
+ * Two launches, no atomics: per-slice partial maxima into work, then re-reduce + threshold + write; run-to-run exact.
+ * NaN input is unspecified.  work: eml_projector_targets_work_floats(B, h, w) floats of scratch (0 for sizes the launcher
+ * refuses).  Any B, h, w >= 1 (h * w <= 2^29, B <= 65535); B == 0 returns 0.
+ * The three entry points of this section are additions within ABI 31 (no existing signature changed; the binding refuses a
+ * library without them by name). */
+size_t eml_projector_targets_work_floats(int B, int h, int w);
+int eml_projector_targets_f32(const float* small, const float* alpha, int B, int h, int w, float* warped, float* map,
+                              float* work, eml_stream_t stream);
+
+/* GenProjector/data.py:70 (`cv2.resize(crop, (128, 128))`, INTER_LINEAR by default): src (B,C,h,w) f32 -> out (B,C,oh,ow)
+ * f32, bilinear without antialiasing.  Each of the four taps is v = alpha ? alpha[b] * src : src (alpha (B) f32 on the
+ * device or NULL), clamped to [0,1] when clip: with the tonemap's P and alpha (eml_tonemap_f32 with out == NULL) this is
+ * the resized tonemapped crop without the full-size one.  Source position in f64: (d + .5) * (n_in / n_out) - .5; below 0:
+ * index 0, weight 0; at or beyond n_in - 1: the last index, weight 0; weights rounded to f32; horizontal interpolation, then
+ * vertical; a weight of 0 returns the tap itself (oh == h and ow == w gives the taps bit for bit).  This is the formula of
+ * cv2's INTER_LINEAR and of F.interpolate(mode="bilinear", align_corners=False); cv2 was not available to compare against,
+ * so parity with it is by formula, not tested.  B * C <= 65535; B == 0 returns 0. */
+int eml_resize_bilinear_f32(const float* src, const float* alpha, int clip, int B, int C, int h, int w, int oh, int ow,
+                            float* out, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
