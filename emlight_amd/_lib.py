@@ -69,6 +69,11 @@ SIGNATURES = {
     "eml_projector_targets_work_floats": (ctypes.c_size_t, [_int, _int, _int]),
     "eml_projector_targets_f32": (_int, [_f32p, _f32p, _int, _int, _int, _f32p, _f32p, _f32p, _stream]),
     "eml_resize_bilinear_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, _int, _int, _f32p, _stream]),
+    # lighting evaluation: sphere renders (diffuse / glossy as an implicit GEMM, mirror lookup) and their metrics
+    "eml_sphere_render_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int]),
+    "eml_sphere_render_f32": (_int, [_f32p, _int, _int, _int, _int, ctypes.c_double, _int, ctypes.c_double, _f32p, _f32p,
+                                     _stream]),
+    "eml_sphere_render_metrics_f64": (_int, [_f32p, _f32p, _int, _int, _int, _f64p, _stream]),
     # GenProjector SphereConv2D
     "eml_sphere_tap_table_f32": (_int, [_f32p, _int, _int, _int, _int, _i32p, _f32p, _stream]),
     "eml_sphere_im2col_f32": (_int, [_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),

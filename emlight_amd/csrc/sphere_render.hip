@@ -1,0 +1,405 @@
+// Lighting evaluation: three spheres (diffuse, matte silver, mirror) lit by an equirectangular panorama and seen by an
+// orthographic camera, and the metrics that compare the renders of a predicted map with those of the true one (RMSE,
+// scale-invariant RMSE, RGB angular error).  The reference tree has no such code (the papers describe it); DESIGN.md
+// section 15 is the definition, tests/sphere_render_oracle.py restates it in float64.
+//
+// Diffuse and glossy are integrals over the panorama: render = K . pano with K (inside pixels x texels) the cosine /
+// Phong-lobe weights times the texel's solid angle, pano (texels x 3B image planes).  K is never stored: a wave owns 32
+// pixels, keeps their n and R in registers, and builds its A fragment of v_mfma_f32_32x32x2_f32 (lane l: pixel l & 31,
+// texel k + (l >> 5)) from a per-texel table (omega, dOmega) that sits in LDS beside the staged panorama chunk; the same
+// chunk feeds both materials' accumulators.  The texels are split over grid.z; the partial tiles go to scratch and a
+// second launch adds them in split order (no atomics: run-to-run exact).  The split depends on (H, W, S) only and an
+// MFMA adds its k terms in order per output element, so an image's render does not depend on the batch it came in.
+// Mirror is a bilinear gather at the reflection direction, coordinates in f64.  Metrics: one workgroup per (image,
+// material), f64 tree reductions in a fixed order (as gt_param.hip), two passes so that si-RMSE is a sum of squares of
+// residuals and not a difference of large sums.
+#include "eml_common.h"
+
+namespace {
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kThreads = 256;
+constexpr int kKC = 64;                 // texels per staged chunk
+constexpr int kColsWG = 96;             // image planes per workgroup: three 32-column MFMA tiles
+constexpr int kRowsWG = 128;            // pixels per workgroup: one 32-row tile per wave
+constexpr int kStride = kKC + 1;        // LDS row of one plane's chunk, padded: the 32 lanes of a half hit 32 banks
+constexpr int kRec = 8;                 // floats per pixel record: n, R, linear pixel index, pad
+constexpr int kMaxSplit = 64;
+constexpr int kSlots = 512;             // 256 CUs x 2 resident workgroups (236 registers: 2 waves per SIMD)
+constexpr int kMaxS = 1024, kMaxH = 4096, kMaxB = 4096;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// Row i of the S x S image: the inside pixels X^2 + Y^2 < S^2 (X = 2j + 1 - S, Y = S - 1 - 2i) are j0 .. S - 1 - j0
+__host__ __device__ inline bool inside_px(int S, int i, int j) {
+  const long long X = 2ll * j + 1 - S, Y = (long long)S - 1 - 2ll * i;
+  return X * X + Y * Y < (long long)S * S;
+}
+__host__ __device__ inline int row_first(int S, int i) {
+  const double Y = (double)S - 1.0 - 2.0 * i;
+  int j0 = (int)ceil(((double)S - 1.0 - sqrt((double)S * S - Y * Y)) * 0.5);
+  if (j0 < 0) j0 = 0;
+  if (j0 > (S - 1) / 2) j0 = (S - 1) / 2;           // the centre column is inside for every row (S >= 2)
+  while (j0 > 0 && inside_px(S, i, j0 - 1)) --j0;
+  while (!inside_px(S, i, j0)) ++j0;
+  return j0;
+}
+inline long inside_count(int S) {
+  long P = 0;
+  for (int i = 0; i < S; ++i) P += S - 2 * row_first(S, i);
+  return P;
+}
+
+struct Plan {
+  long T, P;
+  int nchunks, per, splits, rowgroups, colgroups;
+};
+// the k split is a function of (H, W, S) alone: an image's summation order must not depend on the batch
+inline Plan make_plan(int B, int H, int W, int S) {
+  Plan pl;
+  pl.T = (long)H * W;
+  pl.P = inside_count(S);
+  pl.nchunks = (int)((pl.T + kKC - 1) / kKC);
+  pl.rowgroups = (int)((pl.P + kRowsWG - 1) / kRowsWG);
+  pl.colgroups = (3 * B + kColsWG - 1) / kColsWG;
+  int want = kSlots / pl.rowgroups;                  // one column group's workgroups fit the part at once: no second round
+  if (want > kMaxSplit) want = kMaxSplit;
+  if (want > pl.nchunks) want = pl.nchunks;
+  if (want < 1) want = 1;
+  pl.per = (pl.nchunks + want - 1) / want;
+  pl.splits = (pl.nchunks + pl.per - 1) / pl.per;
+  return pl;
+}
+inline bool size_ok(int B, int H, int W, int S) {
+  return B >= 0 && B <= kMaxB && H >= 1 && H <= kMaxH && W == 2 * H && S >= 2 && S <= kMaxS;
+}
+
+// ------------------------------------------------------------------------------------------------ tables
+// texel (h, w): omega and dOmega in f64, rounded once
+__global__ __launch_bounds__(kThreads) void texel_table_kernel(int H, int W, float4* __restrict__ tab) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= H * W) return;
+  const int h = t / W, w = t - h * W;
+  const double th = ((double)h + 0.5) * kPi / (double)H, ph = ((double)w + 0.5) * (2.0 * kPi) / (double)W;
+  const double st = sin(th);
+  tab[t] = make_float4((float)(st * cos(ph)), (float)(st * sin(ph)), (float)cos(th),
+                       (float)(st * (kPi / (double)H) * (2.0 * kPi / (double)W)));
+}
+
+// n and R of pixel (i, j) in f64: r = (-s, c, 0), u = (0, 0, 1), v = (-c, -s, 0) with (c, s) = (cos, sin) of the azimuth
+__device__ __forceinline__ void pixel_frame(int S, int i, int j, double c, double s, double* n, double* R) {
+  const double px = (double)(2 * j + 1 - S) / (double)S, py = (double)(S - 1 - 2 * i) / (double)S;
+  const double nz = sqrt(1.0 - px * px - py * py);
+  n[0] = px * -s + nz * -c;
+  n[1] = px * c + nz * -s;
+  n[2] = py;
+  R[0] = 2.0 * nz * n[0] + c;
+  R[1] = 2.0 * nz * n[1] + s;
+  R[2] = 2.0 * nz * n[2];
+}
+
+// one workgroup: the compact list of inside pixels in row-major order
+__global__ __launch_bounds__(kThreads) void pixel_list_kernel(int S, double c, double s, float* __restrict__ rec) {
+  __shared__ int start[kMaxS + 1];
+  __shared__ int first[kMaxS];
+  for (int i = threadIdx.x; i < S; i += kThreads) first[i] = row_first(S, i);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int acc = 0;
+    for (int i = 0; i < S; ++i) {
+      start[i] = acc;
+      acc += S - 2 * first[i];
+    }
+    start[S] = acc;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < S; i += kThreads) {
+    const int j0 = first[i], cnt = S - 2 * j0;
+    for (int q = 0; q < cnt; ++q) {
+      double n[3], R[3];
+      pixel_frame(S, i, j0 + q, c, s, n, R);
+      float* o = rec + (size_t)(start[i] + q) * kRec;
+      o[0] = (float)n[0], o[1] = (float)n[1], o[2] = (float)n[2];
+      o[3] = (float)R[0], o[4] = (float)R[1], o[5] = (float)R[2];
+      o[6] = __int_as_float(i * S + j0 + q);
+      o[7] = 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ integrals
+// x^m for x >= 0 (x = 0: 1 when m == 0, as numpy's 0.0 ** 0)
+__device__ __forceinline__ float lobe(float x, float m) {
+  return x > 0.f ? exp2f(m * log2f(x)) : (m == 0.f ? 1.f : 0.f);
+}
+
+// grid (rowgroups, colgroups, splits).  part[split][material 0..1][pixel][column]
+template <bool DIFF, bool GLOSS>
+__global__ __launch_bounds__(kThreads) void integral_kernel(const float* __restrict__ pano, const float4* __restrict__ tab,
+                                                            const float* __restrict__ rec, int P, int T, int N, int per,
+                                                            int nchunks, float m, float* __restrict__ part) {
+  __shared__ float sp[kColsWG * kStride];
+  __shared__ float4 st[kKC];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+  const int p = blockIdx.x * kRowsWG + wave * 32 + r;
+  float nx = 0.f, ny = 0.f, nz = 0.f, Rx = 0.f, Ry = 0.f, Rz = 0.f;      // a row beyond P weighs 0 and is never stored
+  if (p < P) {
+    const float* q = rec + (size_t)p * kRec;
+    nx = q[0], ny = q[1], nz = q[2], Rx = q[3], Ry = q[4], Rz = q[5];
+  }
+  const int col0 = blockIdx.y * kColsWG;
+  const int ncols = N - col0 < kColsWG ? N - col0 : kColsWG;             // > 0 by the grid
+  f32x16 accd[3], accg[3];
+#pragma unroll
+  for (int ct = 0; ct < 3; ++ct)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) accd[ct][e] = 0.f, accg[ct][e] = 0.f;
+
+  const int c_begin = blockIdx.z * per;
+  const int c_end = c_begin + per < nchunks ? c_begin + per : nchunks;
+  constexpr int kLoads = kColsWG * kKC / kThreads;                       // 24 values per thread and chunk
+  float pre[kLoads];
+  float4 pre_t;
+  // chunk c -> registers; a wave reads 64 consecutive texels of one plane
+  auto fetch = [&](int c) {
+    const int k0 = c * kKC;
+#pragma unroll
+    for (int e = 0; e < kLoads; ++e) {
+      const int idx = e * kThreads + tid, cl = idx >> 6, k = k0 + (idx & (kKC - 1));
+      pre[e] = (cl < ncols && k < T) ? pano[(size_t)(col0 + cl) * (size_t)T + k] : 0.f;
+    }
+    pre_t = (tid < kKC && k0 + tid < T) ? tab[k0 + tid] : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  if (c_begin < c_end) fetch(c_begin);
+  for (int c = c_begin; c < c_end; ++c) {
+    __syncthreads();                                                     // the previous chunk has been read
+#pragma unroll
+    for (int e = 0; e < kLoads; ++e) {
+      const int idx = e * kThreads + tid;
+      sp[(idx >> 6) * kStride + (idx & (kKC - 1))] = pre[e];
+    }
+    if (tid < kKC) st[tid] = pre_t;
+    __syncthreads();
+    if (c + 1 < c_end) fetch(c + 1);                                     // in flight while this chunk is computed
+#pragma unroll 2
+    for (int kk = 0; kk < kKC; kk += 2) {
+      const float4 t = st[kk + half];
+      float wd = 0.f, wg = 0.f;
+      if (DIFF) wd = fmaxf(fmaf(nx, t.x, fmaf(ny, t.y, nz * t.z)), 0.f) * t.w;
+      if (GLOSS) wg = lobe(fmaf(Rx, t.x, fmaf(Ry, t.y, Rz * t.z)), m) * t.w;
+#pragma unroll
+      for (int ct = 0; ct < 3; ++ct) {
+        if (ct * 32 < ncols) {                                           // wave-uniform
+          const float b = sp[(ct * 32 + r) * kStride + kk + half];
+          if (DIFF) accd[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wd, b, accd[ct], 0, 0, 0);
+          if (GLOSS) accg[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wg, b, accg[ct], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // C/D of the 32x32 tile: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+  const size_t plane = (size_t)P * (size_t)N;
+  float* pd = part + (size_t)blockIdx.z * 2 * plane;
+#pragma unroll
+  for (int ct = 0; ct < 3; ++ct) {
+    const int cl = ct * 32 + r;
+    if (cl >= ncols) continue;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int row = blockIdx.x * kRowsWG + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+      if (row >= P) continue;
+      const size_t o = (size_t)row * N + col0 + cl;
+      if (DIFF) pd[o] = accd[ct][e];
+      if (GLOSS) pd[plane + o] = accg[ct][e];
+    }
+  }
+}
+
+// out[b][slot][ch][pixel] = scale * sum over the splits, in split order.  grid (ceil(P N / 256), 2): y = material
+__global__ __launch_bounds__(kThreads) void integral_reduce_kernel(const float* __restrict__ part,
+                                                                   const float* __restrict__ rec, int P, int N, int splits,
+                                                                   int S, int M, int slot_d, int slot_g, float scale_d,
+                                                                   float scale_g, float* __restrict__ out) {
+  const int mat = blockIdx.y;
+  const int slot = mat == 0 ? slot_d : slot_g;
+  if (slot < 0) return;
+  const size_t plane = (size_t)P * (size_t)N;
+  const size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= plane) return;
+  const int p = (int)(e / N), col = (int)(e - (size_t)p * N);
+  float s = 0.f;
+  for (int k = 0; k < splits; ++k) s += part[((size_t)k * 2 + mat) * plane + e];
+  const int pix = __float_as_int(rec[(size_t)p * kRec + 6]);
+  const int b = col / 3, ch = col - 3 * b;
+  out[(((size_t)b * M + slot) * 3 + ch) * (size_t)S * S + pix] = s * (mat == 0 ? scale_d : scale_g);
+}
+
+// ------------------------------------------------------------------------------------------------ mirror
+__device__ __forceinline__ float lerp_f32(float a, float b, float t) {
+  return t == 0.f ? a : __fadd_rn(__fmul_rn(a, __fsub_rn(1.f, t)), __fmul_rn(b, t));
+}
+
+// grid (ceil(P / 256), B): a thread looks the panorama up at its pixel's reflection direction, three channels
+__global__ __launch_bounds__(kThreads) void mirror_kernel(const float* __restrict__ pano, const float* __restrict__ rec, int P,
+                                                          int H, int W, int S, int M, int slot, double c, double s,
+                                                          float* __restrict__ out) {
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= P) return;
+  const int b = blockIdx.y;
+  const int pix = __float_as_int(rec[(size_t)p * kRec + 6]);
+  double n[3], R[3];
+  pixel_frame(S, pix / S, pix % S, c, s, n, R);
+  const double th = atan2(sqrt(R[0] * R[0] + R[1] * R[1]), R[2]);
+  double ph = atan2(R[1], R[0]);
+  if (ph < 0.0) ph += 2.0 * kPi;
+  double v = th * (double)H / kPi - 0.5, u = ph * (double)W / (2.0 * kPi) - 0.5;
+  v = v < 0.0 ? 0.0 : (v > (double)(H - 1) ? (double)(H - 1) : v);       // rows clamp
+  const double fv = floor(v), fu = floor(u);
+  const int r0 = (int)fv, r1 = r0 + 1 < H ? r0 + 1 : H - 1;
+  const int c0 = (((int)fu % W) + W) % W, c1 = (c0 + 1) % W;            // columns wrap
+  const float wy = (float)(v - fv), wx = (float)(u - fu);
+  const size_t T = (size_t)H * W;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float* img = pano + ((size_t)b * 3 + ch) * T;
+    const float top = lerp_f32(img[(size_t)r0 * W + c0], img[(size_t)r0 * W + c1], wx);
+    const float bot = lerp_f32(img[(size_t)r1 * W + c0], img[(size_t)r1 * W + c1], wx);
+    out[(((size_t)b * M + slot) * 3 + ch) * (size_t)S * S + pix] = lerp_f32(top, bot, wy);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ metrics
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = kThreads >> 1; s > 0; s >>= 1) {      // fixed-order tree: deterministic
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double out = red[0];
+  __syncthreads();
+  return out;
+}
+
+// grid (M, B): out[b][m] = rmse, si_rmse, angular (degrees), used
+__global__ __launch_bounds__(kThreads) void metrics_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
+                                                           int M, int S, double* __restrict__ out) {
+  __shared__ double red[kThreads];
+  const size_t SS = (size_t)S * S;
+  const size_t base = ((size_t)blockIdx.y * M + blockIdx.x) * 3 * SS;
+  const float* a = pred + base;
+  const float* b = truth + base;
+  double d2 = 0.0, ab = 0.0, aa = 0.0, ang = 0.0, used = 0.0, cnt = 0.0;
+  for (int q = threadIdx.x; q < (int)SS; q += kThreads) {
+    if (!inside_px(S, q / S, q % S)) continue;
+    const double a0 = a[q], a1 = a[SS + q], a2 = a[2 * SS + q], b0 = b[q], b1 = b[SS + q], b2 = b[2 * SS + q];
+    d2 += ((a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1)) + (a2 - b2) * (a2 - b2);
+    const double dot = (a0 * b0 + a1 * b1) + a2 * b2;
+    ab += dot;
+    const double na = (a0 * a0 + a1 * a1) + a2 * a2, nb = (b0 * b0 + b1 * b1) + b2 * b2;
+    aa += na;
+    cnt += 1.0;
+    if (sqrt(na) * sqrt(nb) != 0.0) {
+      const double cx = a1 * b2 - a2 * b1, cy = a2 * b0 - a0 * b2, cz = a0 * b1 - a1 * b0;
+      ang += atan2(sqrt((cx * cx + cy * cy) + cz * cz), dot);
+      used += 1.0;
+    }
+  }
+  d2 = block_sum(d2, red);
+  ab = block_sum(ab, red);
+  aa = block_sum(aa, red);
+  ang = block_sum(ang, red);
+  used = block_sum(used, red);
+  cnt = block_sum(cnt, red);
+  const double sc = aa == 0.0 ? 0.0 : ab / aa;
+  double r2 = 0.0;
+  for (int q = threadIdx.x; q < (int)SS; q += kThreads) {
+    if (!inside_px(S, q / S, q % S)) continue;
+    const double e0 = sc * (double)a[q] - (double)b[q], e1 = sc * (double)a[SS + q] - (double)b[SS + q],
+                 e2 = sc * (double)a[2 * SS + q] - (double)b[2 * SS + q];
+    r2 += (e0 * e0 + e1 * e1) + e2 * e2;
+  }
+  r2 = block_sum(r2, red);
+  if (threadIdx.x == 0) {
+    double* o = out + ((size_t)blockIdx.y * M + blockIdx.x) * 4;
+    o[0] = sqrt(d2 / (3.0 * cnt));
+    o[1] = sqrt(r2 / (3.0 * cnt));
+    o[2] = used == 0.0 ? 0.0 : ang / used * (180.0 / kPi);
+    o[3] = used;
+  }
+}
+
+template <bool DIFF, bool GLOSS>
+void launch_integral(dim3 grid, hipStream_t s, const float* pano, const float4* tab, const float* rec, int P, int T, int N,
+                     int per, int nchunks, float m, float* part) {
+  hipLaunchKernelGGL((integral_kernel<DIFF, GLOSS>), grid, dim3(kThreads), 0, s, pano, tab, rec, P, T, N, per, nchunks, m,
+                     part);
+}
+
+}  // namespace
+
+extern "C" size_t eml_sphere_render_work_floats(int B, int H, int W, int S) {
+  if (!size_ok(B, H, W, S) || B == 0) return 0;
+  const Plan pl = make_plan(B, H, W, S);
+  return 4 * (size_t)pl.T + (size_t)kRec * pl.P + (size_t)pl.splits * 2 * pl.P * 3 * (size_t)B;
+}
+
+extern "C" int eml_sphere_render_f32(const float* pano, int B, int H, int W, int S, double view_azimuth_deg,
+                                     int materials_mask, double phong_m, float* out, float* work, eml_stream_t stream) {
+  if (!pano || !out || !work) return eml::fail(EML_EINVAL, "eml_sphere_render_f32: null pointer");
+  if (W != 2 * H || H < 1) return eml::fail(EML_EINVAL, "eml_sphere_render_f32: W == 2H required (H >= 1), got %d x %d", H, W);
+  if (S < 2) return eml::fail(EML_EINVAL, "eml_sphere_render_f32: S must be at least 2, got %d", S);
+  if (materials_mask <= 0 || materials_mask > EML_SPHERE_ALL)
+    return eml::fail(EML_EINVAL, "eml_sphere_render_f32: materials mask %d is empty or has unknown bits", materials_mask);
+  if (!(phong_m >= 0.0) || !(phong_m <= 1e6) || !(view_azimuth_deg == view_azimuth_deg))
+    return eml::fail(EML_EINVAL, "eml_sphere_render_f32: phong exponent must be in [0, 1e6] and the azimuth a number");
+  if (!size_ok(B, H, W, S))
+    return eml::fail(EML_EINVAL, "eml_sphere_render_f32: grid limits: 0 <= B <= %d, H <= %d, S <= %d", kMaxB, kMaxH, kMaxS);
+  if (B == 0) return EML_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const Plan pl = make_plan(B, H, W, S);
+  const int P = (int)pl.P, T = (int)pl.T, N = 3 * B;
+  const bool diff = materials_mask & EML_SPHERE_DIFFUSE, gloss = materials_mask & EML_SPHERE_GLOSSY,
+             mirror = materials_mask & EML_SPHERE_MIRROR;
+  const int M = (int)diff + (int)gloss + (int)mirror;
+  const int slot_d = diff ? 0 : -1, slot_g = gloss ? (int)diff : -1, slot_m = (int)diff + (int)gloss;
+  float4* tab = reinterpret_cast<float4*>(work);      // torch allocations are 16-byte aligned; 4 T floats keep rec aligned too
+  float* rec = work + 4 * (size_t)T;
+  float* part = rec + (size_t)kRec * P;
+  if (((size_t)work) & 15) return eml::fail(EML_EINVAL, "eml_sphere_render_f32: work must be 16-byte aligned");
+  const double az = view_azimuth_deg * (kPi / 180.0), c = cos(az), sn = sin(az);
+
+  hipError_t e = hipMemsetAsync(out, 0, (size_t)B * M * 3 * (size_t)S * S * sizeof(float), s);   // outside the disc: 0
+  if (e != hipSuccess) return eml::fail(EML_ELAUNCH, "eml_sphere_render_f32(zero): %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(pixel_list_kernel, dim3(1), dim3(kThreads), 0, s, S, c, sn, rec);
+  if (diff || gloss) {
+    hipLaunchKernelGGL(texel_table_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, W, tab);
+    const dim3 grid(pl.rowgroups, pl.colgroups, pl.splits);
+    const float m = (float)phong_m;
+    if (diff && gloss) launch_integral<true, true>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
+    else if (diff) launch_integral<true, false>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
+    else launch_integral<false, true>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
+    int rc = eml::check_launch("eml_sphere_render_f32(integral)");
+    if (rc) return rc;
+    const size_t plane = (size_t)P * N;
+    hipLaunchKernelGGL(integral_reduce_kernel, dim3((unsigned)((plane + kThreads - 1) / kThreads), 2), dim3(kThreads), 0, s,
+                       (const float*)part, (const float*)rec, P, N, pl.splits, S, M, slot_d, slot_g, (float)(1.0 / kPi),
+                       (float)((phong_m + 1.0) / (2.0 * kPi)), out);
+  }
+  if (mirror)
+    hipLaunchKernelGGL(mirror_kernel, dim3((P + kThreads - 1) / kThreads, B), dim3(kThreads), 0, s, pano, (const float*)rec, P,
+                       H, W, S, M, slot_m, c, sn, out);
+  return eml::check_launch("eml_sphere_render_f32");
+}
+
+extern "C" int eml_sphere_render_metrics_f64(const float* pred_render, const float* true_render, int B, int M, int S,
+                                             double* out, eml_stream_t stream) {
+  if (!pred_render || !true_render || !out) return eml::fail(EML_EINVAL, "eml_sphere_render_metrics_f64: null pointer");
+  if (M < 1 || M > 3) return eml::fail(EML_EINVAL, "eml_sphere_render_metrics_f64: M must be 1..3 materials, got %d", M);
+  if (S < 2 || S > kMaxS) return eml::fail(EML_EINVAL, "eml_sphere_render_metrics_f64: S must be 2..%d, got %d", kMaxS, S);
+  if (B < 0 || B > 65535) return eml::fail(EML_EINVAL, "eml_sphere_render_metrics_f64: B must be 0..65535 (grid.y)");
+  if (B == 0) return EML_OK;
+  hipLaunchKernelGGL(metrics_kernel, dim3(M, B), dim3(kThreads), 0, (hipStream_t)stream, pred_render, true_render, M, S, out);
+  return eml::check_launch("eml_sphere_render_metrics_f64");
+}

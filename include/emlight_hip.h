@@ -910,6 +910,36 @@ int eml_projector_targets_f32(const float* small, const float* alpha, int B, int
 int eml_resize_bilinear_f32(const float* src, const float* alpha, int clip, int B, int C, int h, int w, int oh, int ow,
                             float* out, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- lighting evaluation: sphere renders and their metrics
+ * Not in the reference tree (the EMLight papers describe it): three spheres lit by a panorama, seen by an orthographic camera
+ * that looks towards azimuth view_azimuth_deg (180 = the panorama's centre column).  DESIGN.md section 15 is the definition.
+ * pano (B,3,H,W) f32 channel-first on the rasteriser's grid, W == 2H -> out (B,M,3,S,S) f32, M = the number of bits set in
+ * materials_mask, the materials in the order diffuse, glossy, mirror; pixels outside the disc (2j+1-S)^2 + (S-1-2i)^2 < S^2
+ * are 0.  diffuse = (1/pi) sum_t pano[t] max(0, n.w_t) dW_t;  glossy = ((m+1)/2pi) sum_t pano[t] max(0, R.w_t)^m dW_t (Phong
+ * exponent m = phong_m, no horizon clip);  mirror = bilinear lookup at R (coordinates in f64, columns wrap, rows clamp).
+ * The two integrals are one implicit GEMM on the f32 MFMA: the (pixels x texels) weights are built in registers, the texels
+ * are split over workgroups and the partial tiles in `work` are added in split order (no atomics: run-to-run exact; the
+ * split depends on (H, W, S) only, so an image's render does not depend on the batch it is in).
+ * work: eml_sphere_render_work_floats(B, H, W, S) floats, 16-byte aligned (0 for sizes the launcher refuses).
+ * B <= 4096, H <= 4096, 2 <= S <= 1024, 0 <= phong_m <= 1e6; B == 0 returns 0.
+ * The three entry points of this section are additions within ABI 31 (no existing signature changed; the binding refuses a
+ * library without them by name). */
+#define EML_SPHERE_DIFFUSE 1
+#define EML_SPHERE_GLOSSY 2
+#define EML_SPHERE_MIRROR 4
+#define EML_SPHERE_ALL 7
+size_t eml_sphere_render_work_floats(int B, int H, int W, int S);
+int eml_sphere_render_f32(const float* pano, int B, int H, int W, int S, double view_azimuth_deg, int materials_mask,
+                          double phong_m, float* out, float* work, eml_stream_t stream);
+
+/* pred_render, true_render (B,M,3,S,S) f32 (what eml_sphere_render_f32 writes) -> out (B,M,4) f64: rmse, si_rmse, angular
+ * error in degrees, used.  Sums over the P inside pixels (the mask is evaluated from the integer test) and 3 channels in f64,
+ * fixed-order tree reductions: rmse = sqrt(sum (a-b)^2 / 3P);  si_rmse = sqrt(sum (s a - b)^2 / 3P), s = sum ab / sum aa (0 when
+ * sum aa == 0);  angular = mean over the used pixels of atan2(|a_p x b_p|, a_p . b_p) on the RGB vectors, a pixel with
+ * |a_p| |b_p| == 0 is not used, 0 when none is.  One workgroup per (image, material).  M in 1..3, B <= 65535; B == 0 returns 0. */
+int eml_sphere_render_metrics_f64(const float* pred_render, const float* true_render, int B, int M, int S, double* out,
+                                  eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
