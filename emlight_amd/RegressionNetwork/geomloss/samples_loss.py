@@ -99,6 +99,19 @@ def split_watch(device):
     return _split_watches[idx]
 
 
+MAX_EPS = 64   # EML_MAX_EPS: the entries of the caller-owned schedule buffers, and one entry per lane in the kernels
+
+
+def schedule_length(p, diameter, blur, scaling):
+    """Entries of the epsilon schedule ``[d^p] + [exp(e) for e in arange(p ln d, p ln blur, p ln scaling)] + [blur^p]``
+    (``sinkhorn_divergence.py:21-25``) of a diameter ``d > 0``: 2 + the ``numpy.arange`` length, by the kernels' own f64
+    formula (csrc/sinkhorn.hip, ``device_schedule``).  A schedule of more than ``MAX_EPS`` entries is refused, not cut."""
+    if not diameter > 0:
+        raise ValueError("the diameter must be > 0, got %r" % (diameter,))
+    cnt = math.ceil((p * math.log(blur) - p * math.log(diameter)) / (p * math.log(scaling)))
+    return 2 + max(0, cnt)
+
+
 def reach_to_rho(reach, p):
     """``rho = reach**p`` (sinkhorn_divergence.py:35) for a validated ``reach``, or None (balanced) for ``reach=None``.
     ``reach`` must be a number > 0; ``float('inf')`` is accepted and gives lam = 1 (the balanced numbers)."""
@@ -278,6 +291,12 @@ class SamplesLoss(Module):
     With a reach, every softmin of the Sinkhorn loop is damped by ``1 / (1 + eps / reach**p)`` as in EMLight's fork
     (``sinkhorn_divergence.py:35, 43-44, 78-107``); the loss stays the fork's ``<alpha, b_x - a_x> + <beta, a_y - b_y>``
     of the damped duals (``:65-69``), NOT upstream geomloss's unbalanced divergence.
+
+    The epsilon schedule (``schedule_length``) holds at most ``MAX_EPS`` = 64 entries (p = 2, diameter 1, blur .05:
+    ``scaling <= .95``).  A longer one is refused, never cut short: with a fixed ``diameter`` the constructor raises
+    ``ValueError``; with the diameter taken from the data the call returns NaN losses and gradients, and ``forward_raw``
+    reports ``n_eps = -(entries needed)``.  Samples whose diameter is not > 0 (x and y constant and equal; the reference
+    raises there) give NaN too, with ``n_eps = 0``.
     """
 
     def __init__(self, loss="sinkhorn", p=2, blur=.05, reach=None, diameter=None, scaling=.5,
@@ -288,6 +307,12 @@ class SamplesLoss(Module):
         self.rho = reach_to_rho(reach, p)   # validates reach
         self.loss, self.p, self.blur, self.reach = loss, p, blur, reach
         self.diameter, self.scaling = diameter, scaling
+        if diameter is not None and diameter > 0 and blur > 0 and 0 < scaling < 1 and p >= 1:
+            need = schedule_length(p, diameter, blur, scaling)
+            if need > MAX_EPS:
+                raise ValueError("the epsilon schedule of p=%r, diameter=%r, blur=%r, scaling=%r has %d entries; the HIP "
+                                 "kernels hold at most %d (EML_MAX_EPS): raise blur or lower scaling"
+                                 % (p, diameter, blur, scaling, need, MAX_EPS))
         # data-parallel training: derive the eps-schedule from the range of the GLOBAL batch (one 2-float all-reduce per
         # call, no host sync) -- what the single-process reference sees; ignored when ``diameter`` is given
         self.sync_diameter = bool(sync_diameter)

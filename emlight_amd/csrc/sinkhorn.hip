@@ -109,7 +109,7 @@ __device__ __forceinline__ ScanHead schedule_scan_begin(const float* __restrict_
 }
 
 // kD > 1: x, y are (B,N,dim) points (dim <= kD); the diameter is ||max - min||_2 over the per-component ranges of x U y
-// (sinkhorn_divergence.py:9-18), the f32 differences squared and summed in f64; range_dev then holds 2*dim floats
+// (sinkhorn_divergence.py:9-18), the f32 differences squared and summed in f64, the root rounded to f32; range_dev then holds 2*dim floats
 // (dim minima, then dim maxima).
 template <int kWG, bool kFinalBarrier = true, int kD = 1>
 __device__ __forceinline__ void device_schedule(const ScanHead& head, const float* __restrict__ x,
@@ -195,7 +195,7 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
         const double r = (double)(red_hi[c] - red_lo[c]);   // f32 subtraction, as maxs - mins
         s2 += r * r;
       }
-      d = sqrt(s2);
+      d = (double)(float)sqrt(s2);   // .norm() of the f32 ranges is an f32 number, then .item(): what diameter_out reports
     } else if (diameter <= 0.0) {
       lo = red_lo[0];
       hi = red_hi[0];
@@ -209,14 +209,21 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
     int cnt = 0;
     double start = 0.0;
     const double step = p_exp * log_scaling;
+    // no valid schedule (the reference raises or runs a list this ABI cannot hold): refused, never cut -- two NaN entries
+    // (a short loop; the NaN reaches every dual, the loss and the gradients) and n_eps_out = -(entries needed), or 0 when
+    // the diameter is not > 0
+    int refused = 1, code = 0;
     if (d > 0.0) {
       start = p_exp * log(d);
       const double cntd = ceil((p_exp * log_blur - start) / step);  // numpy.arange length
-      cnt = (cntd > 0.0) ? (int)fmin(cntd, (double)(EML_MAX_EPS - 2)) : 0;
+      refused = cntd > (double)(EML_MAX_EPS - 2);
+      if (refused) code = -(int)fmin(cntd + 2.0, 2147483647.0);
+      else cnt = (cntd > 0.0) ? (int)cntd : 0;
     }
     if (tid0 < cnt + 2) {  // one schedule entry per lane (EML_MAX_EPS = 64 = one wave)
       double e;
-      if (tid0 == 0) e = (p_exp == 2) ? d * d : pow(d, (double)p_exp);
+      if (refused) e = (double)NAN;
+      else if (tid0 == 0) e = (p_exp == 2) ? d * d : pow(d, (double)p_exp);
       else if (tid0 == cnt + 1) e = (p_exp == 2) ? blur * blur : pow(blur, (double)p_exp);
       else e = exp(start + (tid0 - 1) * step);
       const float lam = (rho > 0.0) ? (float)(1.0 / (1.0 + e / rho)) : 1.0f;
@@ -228,7 +235,7 @@ __device__ __forceinline__ void device_schedule(const ScanHead& head, const floa
     if (tid0 == 0) {
       *n_eps_l = cnt + 2;
       if (blockIdx.x == 0) {
-        if (n_eps_out) *n_eps_out = cnt + 2;
+        if (n_eps_out) *n_eps_out = refused ? code : cnt + 2;
         if (diameter_out) *diameter_out = (float)d;
       }
     }
@@ -1231,15 +1238,26 @@ __global__ __launch_bounds__(1024) void schedule_kernel(const float* __restrict_
   *diameter_out = (float)d;
   // sinkhorn_divergence.py:21-25, in f64 like numpy
   int k = 0;
-  eps_out[k++] = (float)((p == 2) ? d * d : pow(d, (double)p));
+  double start = 0.0, step = 0.0, cntd = 0.0;
+  int refused = 1, code = 0;   // as device_schedule: a schedule that does not exist or does not fit is refused, never cut
   if (d > 0.0) {
-    const double start = p * log(d), stop = p * log(blur), step = p * log(scaling);
-    const double cntd = ceil((stop - start) / step);  // numpy.arange length
-    const int cnt = (cntd > 0.0) ? (int)fmin(cntd, (double)(EML_MAX_EPS - 2)) : 0;
-    for (int e = 0; e < cnt; ++e) eps_out[k++] = (float)exp(start + e * step);
+    start = p * log(d);
+    step = p * log(scaling);
+    cntd = ceil((p * log(blur) - start) / step);  // numpy.arange length
+    refused = cntd > (double)(EML_MAX_EPS - 2);
+    if (refused) code = -(int)fmin(cntd + 2.0, 2147483647.0);
   }
-  eps_out[k++] = (float)((p == 2) ? blur * blur : pow(blur, (double)p));
-  *n_eps_out = k;
+  if (refused) {
+    eps_out[k++] = NAN;
+    eps_out[k++] = NAN;
+    *n_eps_out = code;
+  } else {
+    eps_out[k++] = (float)((p == 2) ? d * d : pow(d, (double)p));
+    const int cnt = (cntd > 0.0) ? (int)cntd : 0;
+    for (int e = 0; e < cnt; ++e) eps_out[k++] = (float)exp(start + e * step);
+    eps_out[k++] = (float)((p == 2) ? blur * blur : pow(blur, (double)p));
+    *n_eps_out = k;
+  }
   for (; k < EML_MAX_EPS; ++k) eps_out[k] = 0.f;
 }
 
@@ -1282,6 +1300,24 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict
 
 }  // namespace
 
+namespace {
+// Entries of the schedule of a KNOWN diameter (> 0), the kernels' f64 formula on the host: 2 + the numpy.arange length.
+double host_schedule_entries(int p, double diameter, double blur, double scaling) {
+  const double cntd = std::ceil((p * std::log(blur) - p * std::log(diameter)) / (p * std::log(scaling)));
+  return 2.0 + (cntd > 0.0 ? cntd : 0.0);
+}
+// EML_EINVAL for a fixed diameter whose schedule does not fit the caller's EML_MAX_EPS-entry buffers (0: fits, or the
+// diameter comes from the data and the kernel reports it through n_eps_out)
+int refuse_long_schedule(const char* who, int p, double diameter, double blur, double scaling) {
+  if (!(diameter > 0.0)) return 0;
+  const double need = host_schedule_entries(p, diameter, blur, scaling);
+  if (!(need <= (double)EML_MAX_EPS))
+    return eml::fail(EML_EINVAL, "%s: the epsilon schedule of p=%d, diameter=%g, blur=%g, scaling=%g has %.0f entries; "
+                     "EML_MAX_EPS = %d", who, p, diameter, blur, scaling, need, EML_MAX_EPS);
+  return 0;
+}
+}  // namespace
+
 extern "C" int eml_emd_anchor_cost_f32(const float* anchors, float* M, int N, eml_stream_t stream) {
   if (!anchors || !M || N < 1 || N > 16384) return eml::fail(EML_EINVAL, "eml_emd_anchor_cost_f32: bad arguments");
   hipLaunchKernelGGL(anchor_cost_kernel, dim3((N * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, anchors, M, N);
@@ -1296,6 +1332,7 @@ extern "C" int eml_sinkhorn_schedule_f32(const float* x, const float* y, long n,
     return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_f32: need x, y, n>=1 when diameter is not given");
   if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
     return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_f32: need blur>0, 0<scaling<1, p>=1");
+  if (int rc = refuse_long_schedule("eml_sinkhorn_schedule_f32", p, diameter, blur, scaling)) return rc;
   hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, y, n, blur, scaling, p,
                      diameter, range_lo_hi, eps_out, n_eps_out, diameter_out);
   return eml::check_launch("eml_sinkhorn_schedule_f32");
@@ -1446,6 +1483,7 @@ extern "C" int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const fl
   if (B < 0 || N < 1 || N > 2048) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: need 1<=N<=2048 (got %d)", N);
   if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
     return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: need blur>0, 0<scaling<1, p>=1");
+  if (int rc = refuse_long_schedule("eml_sinkhorn_fwd_f32", p, diameter, blur, scaling)) return rc;
   if (B == 0) return EML_OK;
   const double log_blur = std::log(blur), log_scaling = std::log(scaling);   // f64 like numpy; only log(diameter) is data
   const int NP = round_up4(N) + kJPT;
@@ -1539,6 +1577,7 @@ extern "C" int eml_sinkhorn_schedule_dim_f32(const float* x, const float* y, lon
     return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: need x, y, 1<=n<2^28 when diameter is not given");
   if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
     return eml::fail(EML_EINVAL, "eml_sinkhorn_schedule_dim_f32: need blur>0, 0<scaling<1, p>=1");
+  if (int rc = refuse_long_schedule("eml_sinkhorn_schedule_dim_f32", p, diameter, blur, scaling)) return rc;
   hipLaunchKernelGGL(schedule_dim_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, y, (int)std::max(n, 1L), D, blur,
                      std::log(blur), std::log(scaling), p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out);
   return eml::check_launch("eml_sinkhorn_schedule_dim_f32");
@@ -1599,6 +1638,7 @@ extern "C" int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const fl
   if (B < 0 || N < 1 || N > 2048) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need 1<=N<=2048 (got %d)", N);
   if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
     return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need blur>0, 0<scaling<1, p>=1");
+  if (int rc = refuse_long_schedule("eml_sinkhorn_fwd_dim_f32", p, diameter, blur, scaling)) return rc;
   if (B == 0) return EML_OK;
   const double log_blur = std::log(blur), log_scaling = std::log(scaling);
   const hipStream_t s = (hipStream_t)stream;

@@ -99,7 +99,16 @@ int eml_emd_anchor_cost_f32(const float* anchors, float* M, int N, eml_stream_t 
  * evaluated in f64 exactly as numpy does, stored as f32.
  * Replaces max_diameter / scaling_parameters / epsilon_schedule,
  * RegressionNetwork/geomloss/sinkhorn_divergence.py:9-36.
- * Outputs: eps_out[EML_MAX_EPS], *n_eps_out (device int), *diameter_out (device float). */
+ * Outputs: eps_out[EML_MAX_EPS], *n_eps_out (device int), *diameter_out (device float).
+ * The cap: a schedule has 2 + max(0, ceil((ln blur - ln d) / ln scaling)) entries and must fit the EML_MAX_EPS = 64 entries of
+ * the caller's buffers (p = 2, d = 1, blur = .05: scaling <= .95).  One that does not fit is REFUSED, never cut short --
+ * here and in every eml_sinkhorn_fwd_* call:
+ *   diameter > 0 (known on the host)   the call returns EML_EINVAL and launches nothing;
+ *   diameter from the data             *n_eps_out = -(entries needed), two NaN entries in eps_out (the rest zero here),
+ *                                      and a loss call runs its two-entry loop on them: every dual, loss and gradient
+ *                                      comes back NaN, never a finite number of a cut schedule;
+ *   derived diameter not > 0 (x and y constant and equal; the reference raises in numpy.arange)
+ *                                      the same NaN outputs with *n_eps_out = 0. */
 int eml_sinkhorn_schedule_f32(const float* x, const float* y, long n, double blur,
                               double scaling, int p, double diameter, const float* range_lo_hi,
                               float* eps_out, int* n_eps_out, float* diameter_out, eml_stream_t stream);

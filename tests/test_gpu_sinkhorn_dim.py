@@ -47,16 +47,19 @@ def _weights(B, n, seed=7):
     return a / a.sum(1, keepdim=True), b / b.sum(1, keepdim=True)
 
 
-def loss_f64(x, y, M, blur, reach=None, a=None, b=None, p=2, scaling=.5):
+def loss_f64(x, y, M, blur, reach=None, a=None, b=None, p=2, scaling=.5, dtype=torch.float64, aux=None):
     """The fork's Sinkhorn loss in f64 with autograd (sinkhorn_divergence.py:9-109): the cost of ``oracle.spherical_cost``
     (any D), softmins damped by lam = 1 / (1 + eps / reach**p) when a reach is given, the duals detached into the last
-    extrapolation, loss <a, b_x - a_x> + <b, a_y - b_y>.  The diameter is that of the f32 inputs, as the kernel sees them."""
+    extrapolation, loss <a, b_x - a_x> + <b, a_y - b_y>.  The diameter is that of the f32 inputs, as the kernel sees them.
+    ``dtype``: the precision of ``x, y`` (and of ``a, b`` when given) -- torch.float32 restates the reference's own
+    arithmetic; ``aux``: a dict that receives ``eps_s``, ``diameter`` and the four final ``duals`` (4, B, N)."""
     B, N, _ = x.shape
-    eps_s = oracle.epsilon_schedule(p, oracle.max_diameter(x.detach().float(), y.detach().float()), blur, scaling)
+    diameter = oracle.max_diameter(x.detach().float(), y.detach().float())
+    eps_s = oracle.epsilon_schedule(p, diameter, blur, scaling)
     lam = (lambda e: 1.0) if reach is None else (lambda e: 1.0 / (1.0 + e / reach ** p))
-    M = M.double()
-    a = torch.full((B, N), 1.0 / N, dtype=torch.float64) if a is None else a
-    b = torch.full((B, N), 1.0 / N, dtype=torch.float64) if b is None else b
+    M = M.to(dtype)
+    a = torch.full((B, N), 1.0 / N, dtype=dtype) if a is None else a
+    b = torch.full((B, N), 1.0 / N, dtype=dtype) if b is None else b
     la, lb = oracle.log_weights(a.detach()), oracle.log_weights(b.detach())
     C = lambda u, v: oracle.spherical_cost(u, v, M)   # noqa: E731
     C_xx, C_yy, C_xy, C_yx = C(x, x.detach()), C(y, y.detach()), C(x, y.detach()), C(y, x.detach())
@@ -71,6 +74,8 @@ def loss_f64(x, y, M, blur, reach=None, a=None, b=None, p=2, scaling=.5):
             a_x, b_y, a_y, b_x = .5 * (a_x + at_x), .5 * (b_y + bt_y), .5 * (a_y + at_y), .5 * (b_x + bt_x)
     a_x, b_y = lam(e) * sm(e, C_xx, (la + a_x / e).detach()), lam(e) * sm(e, C_yy, (lb + b_y / e).detach())
     a_y, b_x = lam(e) * sm(e, C_yx, (la + b_x / e).detach()), lam(e) * sm(e, C_xy, (lb + a_y / e).detach())
+    if aux is not None:
+        aux.update(eps_s=eps_s, diameter=diameter, duals=torch.stack([a_x, b_y, a_y, b_x]).detach())
     return oracle.sinkhorn_cost(a, b, a_x, b_y, a_y, b_x)
 
 

@@ -186,3 +186,44 @@ def test_gt_parametrisation_matches_reference():
             assert int(mp.sum()) == int(g["%s/%d/map_count" % (name, b)])
             for k in ("distribution", "intensity", "rgb_ratio", "ambient"):
                 np.testing.assert_allclose(para[k], g["%s/%d/%s" % (name, b, k)], rtol=1e-12, atol=1e-14, err_msg=k)
+
+
+# ---- the constructor's other arguments (p, scaling, blur) and inputs off the simplex: tests/golden/sinkhorn_regimes.npz
+from tests.golden.make_golden_sinkhorn_regimes import REGIME_CASES  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def golden_sinkhorn_regimes():
+    from tests.conftest import Golden
+    return Golden("sinkhorn_regimes")
+
+
+@pytest.mark.parametrize("case", [c[0] for c in REGIME_CASES])
+def test_samples_loss_matches_reference_at_other_p_scaling_and_input_scales(golden_sinkhorn_regimes, case):
+    """``oracle.samples_loss(p=, scaling=, blur=)`` -- and, for the D = 3, reach and weighted cases, the f64 restatement
+    ``loss_f64`` of tests/test_gpu_sinkhorn_dim.py that the GPU tests compare against -- reproduce the reference run with
+    those arguments: the schedule to 1e-15 (both are numpy f64), the loss to 1e-7 (the reference computes in f32)."""
+    from tests.test_gpu_sinkhorn_dim import loss_f64
+    c = golden_sinkhorn_regimes.case(case)
+    p, scaling, blur, reach = int(c["p"]), float(c["scaling"]), float(c["blur"]), float(c["reach"]) or None
+    B, n, D = c["x"].shape
+    M = oracle.anchor_cost_matrix(n)
+    y = torch.from_numpy(c["y"])
+    gref = c["grad_x"]
+    if D == 1 and reach is None and "alpha" not in c:
+        x = torch.from_numpy(c["x"]).requires_grad_(True)
+        loss, aux = oracle.samples_loss(x, y, M, blur=blur, scaling=scaling, p=p, return_aux=True)
+        np.testing.assert_allclose(np.asarray(aux["eps_s"]), c["eps_s"], rtol=1e-15)
+        assert abs(aux["diameter"] - float(c["diameter"])) <= 1e-7 * max(1.0, float(c["diameter"]))
+        for got, want in zip(aux["duals"], c["duals"]):
+            np.testing.assert_allclose(got.detach().numpy(), want, rtol=0, atol=1e-6 * max(1.0, np.abs(want).max()))
+    else:
+        x = torch.from_numpy(c["x"]).double().requires_grad_(True)
+        a = torch.from_numpy(c["alpha"]).double() if "alpha" in c else None
+        b = torch.from_numpy(c["beta"]).double() if "alpha" in c else None
+        loss = loss_f64(x, y.double(), M, blur, reach, a, b, p=p, scaling=scaling)
+        diam = oracle.max_diameter(torch.from_numpy(c["x"]), y)
+        np.testing.assert_allclose(np.asarray(oracle.epsilon_schedule(p, diam, blur, scaling)), c["eps_s"], rtol=1e-15)
+    np.testing.assert_allclose(loss.detach().numpy(), c["loss"], rtol=0, atol=1e-7)
+    loss.sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), gref, rtol=1e-4, atol=2e-5 * np.abs(gref).max())
