@@ -74,6 +74,12 @@ SIGNATURES = {
     "eml_sphere_render_f32": (_int, [_f32p, _int, _int, _int, _int, ctypes.c_double, _int, ctypes.c_double, _f32p, _f32p,
                                      _stream]),
     "eml_sphere_render_metrics_f64": (_int, [_f32p, _f32p, _int, _int, _int, _f64p, _stream]),
+    # spherical needlets: basis matrix, analysis / synthesis (each the other's adjoint), per-level hard threshold
+    "eml_needlet_basis_f32": (_int, [_f32p, _int, _f32p, _f32p, _int, _f32p, _stream]),
+    "eml_needlet_work_floats": (ctypes.c_size_t, [_int, _int, _int]),
+    "eml_needlet_analysis_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _f32p, _f32p, _int, _f32p, _f32p, _stream]),
+    "eml_needlet_synthesis_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _f32p, _f32p, _int, _f32p, _stream]),
+    "eml_needlet_sparsify_f32": (_int, [_f32p, _int, _int, _int, ctypes.c_double, _f32p, _i32p, _stream]),
     # GenProjector SphereConv2D
     "eml_sphere_tap_table_f32": (_int, [_f32p, _int, _int, _int, _int, _i32p, _f32p, _stream]),
     "eml_sphere_im2col_f32": (_int, [_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),

@@ -949,6 +949,40 @@ int eml_sphere_render_f32(const float* pano, int B, int H, int W, int S, double 
 int eml_sphere_render_metrics_f64(const float* pred_render, const float* true_render, int B, int M, int S, double* out,
                                   eml_stream_t stream);
 
+/* ---------------------------------------------------------------- spherical needlets (the reference's Needlets/ folder)
+ * The basis of sphere_needlets.py:236 (`SN_matrix = [Y_00, psi_0., ..., psi_jmax.]`, B = 2): K = 4^(jmax+2) - 3 rows, row 0 =
+ * Y_00 = 1/sqrt(4 pi), then for each level j the 12 * 4^j needlets centred at the HEALPix (Nside = 2^j, RING) pixel centres.
+ * spneedlet_eval (sphere_needlets.py:182-191, :34-104) is, by the addition theorem, the zonal sum
+ *   psi_jk(x) = sum_{l=0..2^(jmax+1)} ctab[j+1][l] P_l(x . xi_jk),  ctab[j+1][l] = sqrt(4 pi / Npix_j) b(l / 2^j) (2l+1) / (4 pi)
+ * (b = fun_b, :10-29; zero for l = 0 and beyond 2^(j+1)); ctab[0] = {1/sqrt(4 pi), 0, ...} is Y_00.  DESIGN.md section 16.
+ * Tables, f32 on the device, made by the caller in f64: centres (K,4) = unit vector + table row (0 for Y_00, j + 1 for level
+ * j), 16-byte aligned; ctab (jmax+2, 33); dirs (P,3) unit vectors of the pixels; weights (P) or NULL (= 1).  jmax in 0..4,
+ * 1 <= P <= 2^24, B <= 65535; B == 0 returns 0 and launches nothing.
+ * The five entry points of this section are additions within ABI 31 (no existing signature changed; the binding refuses a
+ * library without them by name). */
+/* out (P,K) = psi_k(x_p): the reference's SN_matrix at arbitrary directions (sphere_needlets.py:196-238). */
+int eml_needlet_basis_f32(const float* dirs, int P, const float* centres, const float* ctab, int jmax, float* out,
+                          eml_stream_t stream);
+/* gt_gen_j3.py:39-43 / mat_gen2.py:36-41: pano (B,3,P) -> coeffs (B,K,3) = sum_p psi_k(x_p) weights[p] pano[b,c,p].  An implicit
+ * GEMM on the f32 MFMA (rows = basis functions, built in registers; columns = the 3B planes); the pixels are split over
+ * workgroups by a plan that depends on (P, jmax) only and the partial tiles in `work` are added in split order: no atomics,
+ * run-to-run exact, and an image's coefficients do not depend on its batch.  work: eml_needlet_work_floats(P, jmax, B) floats,
+ * 16-byte aligned (0 for sizes the launcher refuses).  Also the gradient of eml_needlet_synthesis_f32 w.r.t. coeffs. */
+size_t eml_needlet_work_floats(int P, int jmax, int B);
+int eml_needlet_analysis_f32(const float* pano, const float* dirs, const float* weights, int B, int P, const float* centres,
+                             const float* ctab, int jmax, float* coeffs, float* work, eml_stream_t stream);
+/* mat_gen2.py:55 (`np.dot(SN_Matrix, SN_Coeffs)`): coeffs (B,K,3) -> rec (B,3,P) = weights[p] sum_k psi_k(x_p) coeffs[b,k,c]
+ * (weights == NULL: the reference's form).  The same GEMM with the pixels as rows; no split.  Also the gradient of
+ * eml_needlet_analysis_f32 w.r.t. pano. */
+int eml_needlet_synthesis_f32(const float* coeffs, const float* dirs, const float* weights, int B, int P, const float* centres,
+                              const float* ctab, int jmax, float* rec, eml_stream_t stream);
+/* mat_gen2.py:43-51: for each image and each level j with bit j of levels_mask set, out = |c| > (float)ratio * max|c| ? c : 0
+ * (f32, strict; the maximum over the level's rows and the three channels); the other rows are copied.  kept (B, jmax+1) i32:
+ * the entries kept per level (all 36 * 4^j of an unselected one).  0 <= ratio <= 1.  One workgroup per (image, level);
+ * out may be coeffs. */
+int eml_needlet_sparsify_f32(const float* coeffs, int B, int jmax, int levels_mask, double ratio, float* out, int* kept,
+                             eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
