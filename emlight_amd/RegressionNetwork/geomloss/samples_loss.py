@@ -130,24 +130,23 @@ def reach_to_rho(reach, p):
 
 
 def sinkhorn_outputs(B, N, dev, need_gx=True, need_gy=False, D=1):
-    """Device buffers one ``eml_sinkhorn_fwd_ex_f32`` call writes (the caller owns every buffer, include/emlight_hip.h).
-    ``D > 1``: the buffers of ``eml_sinkhorn_fwd_dim_f32`` -- gradients ``(B, N, D)``, its own scratch size."""
+    """Device buffers one forward call writes (the caller owns every buffer, include/emlight_hip.h): those of
+    ``eml_sinkhorn_fwd_ex_f32`` / ``_rho_f32`` for ``D = 1``, those of ``eml_sinkhorn_fwd_dim_f32`` -- gradients
+    ``(B, N, D)``, its own scratch size -- for ``D > 1``."""
     f32 = dict(dtype=torch.float32, device=dev)
-    if D != 1:
-        work = torch.empty(max(int(_lib.lib().eml_sinkhorn_dim_work_floats(B, N, D)), (4 + 4 * D) * B * N), **f32)
-        return {"eps_s": torch.empty(64, **f32), "n_eps": torch.empty(1, dtype=torch.int32, device=dev),
-                "diameter": torch.empty(1, **f32), "loss": torch.empty(B, **f32),
-                "gx": torch.empty(B, N, D, **f32) if need_gx else None,
-                "gy": torch.empty(B, N, D, **f32) if need_gy else None, "work": work}
-    n_work = max(int(_lib.lib().eml_sinkhorn_work_floats(B, N)), 8 * B * N)
+    # scratch size from the library (duals, expectation rows; D = 1: the small-batch kernel's exchange buffer and status
+    # words too); never less than the planes every kernel writes
+    if D == 1:
+        n_work = max(int(_lib.lib().eml_sinkhorn_work_floats(B, N)), 8 * B * N)
+    else:
+        n_work = max(int(_lib.lib().eml_sinkhorn_dim_work_floats(B, N, D)), (4 + 4 * D) * B * N)
     work = torch.empty(n_work, **f32)
-    if split_eligible(N) and n_work > 24 * B * N:
+    if D == 1 and split_eligible(N) and n_work > 24 * B * N:
         work[24 * B * N:].zero_()   # the status word: only calls that take the split path reset it
+    grad = (B, N) if D == 1 else (B, N, D)
     return {"eps_s": torch.empty(64, **f32), "n_eps": torch.empty(1, dtype=torch.int32, device=dev),
             "diameter": torch.empty(1, **f32), "loss": torch.empty(B, **f32),
-            "gx": torch.empty(B, N, **f32) if need_gx else None, "gy": torch.empty(B, N, **f32) if need_gy else None,
-            # scratch size from the library (duals, expectation rows, the small-batch kernel's exchange buffer and status
-            # word); never less than the (8,B,N) planes every kernel writes
+            "gx": torch.empty(grad, **f32) if need_gx else None, "gy": torch.empty(grad, **f32) if need_gy else None,
             "work": work}
 
 
@@ -180,59 +179,38 @@ def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=T
                  range_lo_hi=None, flags=None, rho=None, want_lam=False):
     """One call into the HIP library; returns every device-side output (no autograd).  ``out``: buffers from
     ``sinkhorn_outputs`` to write into (a timing loop passes them so that no allocation sits between launches).
-    ``range_lo_hi``: device (2,) tensor from ``global_range`` -- the kernel folds it into its own scan.
+    ``range_lo_hi``: device tensor from ``global_range`` -- the kernel folds it into its own scan.
+    ``x, y`` of shape ``(B, N)`` (1-D points) or ``(B, N, D)`` (``eml_sinkhorn_fwd_dim_f32``; the split kernel and its
+    watch do not apply there).
     ``flags``: EML_SINKHORN_* of the C ABI; default: whatever the split kernel's watch says (``_SplitWatch``).
-    ``rho``: reach**p of unbalanced OT, or None (balanced: the call is ``eml_sinkhorn_fwd_ex_f32``, as it always was);
-    ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when balanced).
-    ``x, y`` of shape ``(B, N)`` (1-D points) or ``(B, N, D)`` with ``D > 1`` (``eml_sinkhorn_fwd_dim_f32``)."""
-    if x.dim() == 3:
-        return _sinkhorn_raw_dim(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx, need_gy, out,
-                                 range_lo_hi, flags, rho, want_lam)
+    ``rho``: reach**p of unbalanced OT, or None (balanced; for 1-D points the call is ``eml_sinkhorn_fwd_ex_f32``, as
+    it always was); ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when
+    balanced)."""
     L = _lib.lib()
-    B, N = x.shape
-    o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy)
-    watched = flags is None and split_eligible(N)
-    if flags is None:
-        flags = split_watch(x.device).flags() if watched else 0
-    args = (_lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
-            float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
-            _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]),
-            _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N, int(flags))
-    lam = None
-    if rho is None and not want_lam:
-        _lib.check(L.eml_sinkhorn_fwd_ex_f32(*args, _lib.current_stream()), "eml_sinkhorn_fwd_ex_f32")
-    else:
-        if want_lam:
-            lam = o.get("lam")
-            lam = torch.empty(64, dtype=torch.float32, device=x.device) if lam is None else lam
-        _lib.check(L.eml_sinkhorn_fwd_rho_f32(*args, float(rho) if rho is not None else 0.0, _lib.ptr(lam),
-                                              _lib.current_stream()), "eml_sinkhorn_fwd_rho_f32")
-    if watched and o["work"].numel() > 24 * B * N:
-        split_watch(x.device).after_call(o["work"], B, N)
-    r = {"loss": o["loss"], "gx": o["gx"], "gy": o["gy"], "eps_s": o["eps_s"], "n_eps": o["n_eps"],
-         "diameter": o["diameter"], "duals": o["work"][:4 * B * N].view(4, B, N), "work": o["work"]}
-    if lam is not None:
-        r["lam"] = lam
-    return r
-
-
-def _sinkhorn_raw_dim(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx, need_gy, out, range_lo_hi, flags,
-                      rho, want_lam):
-    """``sinkhorn_raw`` for ``(B, N, D)`` points: one ``eml_sinkhorn_fwd_dim_f32`` call (the split kernel and its watch do
-    not apply; ``flags`` is passed through)."""
-    L = _lib.lib()
-    B, N, D = x.shape
-    o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy, D=D)
+    B, N = x.shape[:2]
+    D = x.shape[2] if x.dim() == 3 else None   # None: 1-D points through the entries that take no D
+    o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy, D=D or 1)
+    watched = D is None and flags is None and split_eligible(N)
+    if watched:
+        flags = split_watch(x.device).flags()
     lam = None
     if want_lam:
         lam = o.get("lam")
         lam = torch.empty(64, dtype=torch.float32, device=x.device) if lam is None else lam
-    _lib.check(L.eml_sinkhorn_fwd_dim_f32(
-        _lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
-        float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
-        _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]),
-        _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N, D, int(flags or 0),
-        float(rho) if rho is not None else 0.0, _lib.ptr(lam), _lib.current_stream()), "eml_sinkhorn_fwd_dim_f32")
+    args = (_lib.ptr(x), _lib.ptr(y), _lib.ptr(M), _lib.ptr(Mt), _lib.ptr(alpha), _lib.ptr(beta),
+            float(blur), float(scaling), int(p), float(diameter) if diameter is not None else -1.0,
+            _lib.ptr(range_lo_hi), _lib.ptr(o["eps_s"]), _lib.ptr(o["n_eps"]), _lib.ptr(o["diameter"]), _lib.ptr(o["loss"]),
+            _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N)
+    flags, stream = int(flags or 0), _lib.current_stream()
+    rho_lam = (float(rho) if rho is not None else 0.0, _lib.ptr(lam))
+    if D is not None:
+        _lib.check(L.eml_sinkhorn_fwd_dim_f32(*args, D, flags, *rho_lam, stream), "eml_sinkhorn_fwd_dim_f32")
+    elif rho is None and not want_lam:
+        _lib.check(L.eml_sinkhorn_fwd_ex_f32(*args, flags, stream), "eml_sinkhorn_fwd_ex_f32")
+    else:
+        _lib.check(L.eml_sinkhorn_fwd_rho_f32(*args, flags, *rho_lam, stream), "eml_sinkhorn_fwd_rho_f32")
+    if watched and o["work"].numel() > 24 * B * N:
+        split_watch(x.device).after_call(o["work"], B, N)
     r = {"loss": o["loss"], "gx": o["gx"], "gy": o["gy"], "eps_s": o["eps_s"], "n_eps": o["n_eps"],
          "diameter": o["diameter"], "duals": o["work"][:4 * B * N].view(4, B, N), "work": o["work"]}
     if lam is not None:
@@ -368,50 +346,37 @@ class SamplesLoss(Module):
             raise ValueError("the point dimension D must be 1 <= D <= %d (EML_SINKHORN_MAX_DIM), got D = %d" % (MAX_DIM, D))
         return D
 
+    def _samples(self, x, y):
+        """``x, y`` as the kernels read them: ``(B, N)`` for 1-D points, ``(B, N, D)`` for D > 1."""
+        if not (x.dim() == 3 and x.shape[-1] > 1):
+            x, y = x.reshape(x.shape[0], self.N), y.reshape(x.shape[0], self.N)
+        return _lib.require_gpu_tensor(x, "x"), _lib.require_gpu_tensor(y, "y")
+
+    def _cost_and_range(self, x, y):
+        """The cost matrices on the samples' device and, under ``sync_diameter``, the range of the global batch
+        (``(2,)``, or ``(2*D,)`` for D > 1)."""
+        M, Mt = self.cost_matrix(x.device)
+        return M, Mt, global_range(x, y) if (self.sync_diameter and self.diameter is None) else None
+
     def forward(self, *args):
         a, x, b, y = self.process_args(*args)
-        if self._check_samples(x, y) > 1:
-            return self._forward_dim(a, x, b, y)
+        self._check_samples(x, y)
+        x, y = self._samples(x, y)
         B = x.shape[0]
-        x2 = _lib.require_gpu_tensor(x.reshape(B, self.N), "x")
-        y2 = _lib.require_gpu_tensor(y.reshape(B, self.N), "y")
         if B == 0:
-            return x2.new_zeros(0) + 0.0 * (x2.sum() + y2.sum())
-        a2 = None if a is None else _lib.require_gpu_tensor(a.reshape(B, self.N), "alpha")
-        b2 = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
-        M, Mt = self.cost_matrix(x2.device)
-        rng = global_range(x2, y2) if (self.sync_diameter and self.diameter is None) else None
-        return _SinkhornDivergence.apply(x2, y2, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
-
-    def _forward_dim(self, a, x, b, y):
-        """``forward`` on ``(B, N, D)`` samples, D > 1: gradients ``(B, N, D)``, the (2*D,) range under ``sync_diameter``."""
-        B = x.shape[0]
-        x3 = _lib.require_gpu_tensor(x, "x")
-        y3 = _lib.require_gpu_tensor(y, "y")
-        if B == 0:
-            return x3.new_zeros(0) + 0.0 * (x3.sum() + y3.sum())
-        a2 = None if a is None else _lib.require_gpu_tensor(a.reshape(B, self.N), "alpha")
-        b2 = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
-        M, Mt = self.cost_matrix(x3.device)
-        rng = global_range(x3, y3) if (self.sync_diameter and self.diameter is None) else None
-        return _SinkhornDivergence.apply(x3, y3, a2, b2, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
+            return x.new_zeros(0) + 0.0 * (x.sum() + y.sum())
+        a = None if a is None else _lib.require_gpu_tensor(a.reshape(B, self.N), "alpha")
+        b = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
+        M, Mt, rng = self._cost_and_range(x, y)
+        return _SinkhornDivergence.apply(x, y, a, b, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
 
     def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None, want_lam=False):
         """Every device output of one call (loss, unit grads, schedule, duals; with ``want_lam`` the dampening schedule
-        ``lam`` next to ``eps_s``) -- for parity tests and timing.  ``(B, N, D)`` samples with D > 1: gradients
-        ``(B, N, D)``."""
+        ``lam`` next to ``eps_s``) -- for parity tests and timing.  1-D points may come as ``(B, N)`` or ``(B, N, 1)``;
+        ``(B, N, D)`` samples with D > 1 give gradients ``(B, N, D)``."""
         if x.dim() == 3 and x.shape[-1] > 1:
             self._check_samples(x, y)
-            x3 = _lib.require_gpu_tensor(x, "x")
-            y3 = _lib.require_gpu_tensor(y, "y")
-            M, Mt = self.cost_matrix(x3.device)
-            rng = global_range(x3, y3) if (self.sync_diameter and self.diameter is None) else None
-            return sinkhorn_raw(x3, y3, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
-                                need_gx, need_gy, out, range_lo_hi=rng, flags=flags, rho=self.rho, want_lam=want_lam)
-        B = x.shape[0]
-        x2 = _lib.require_gpu_tensor(x.reshape(B, self.N), "x")
-        y2 = _lib.require_gpu_tensor(y.reshape(B, self.N), "y")
-        M, Mt = self.cost_matrix(x2.device)
-        rng = global_range(x2, y2) if (self.sync_diameter and self.diameter is None) else None
-        return sinkhorn_raw(x2, y2, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
+        x, y = self._samples(x, y)
+        M, Mt, rng = self._cost_and_range(x, y)
+        return sinkhorn_raw(x, y, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
                             need_gx, need_gy, out, range_lo_hi=rng, flags=flags, rho=self.rho, want_lam=want_lam)

@@ -25,11 +25,12 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// Call after a kernel launch: turns a launch error into a return code + message.
-inline int check_launch(const char* what) {
+// Call after a kernel launch: turns a launch error into a return code + message, "what: error" or "what(step): error".
+inline int check_launch(const char* what, const char* step = nullptr) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    fail(EML_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    if (step) fail(EML_ELAUNCH, "%s(%s): %s", what, step, hipGetErrorString(e));
+    else fail(EML_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return (int)e > 0 ? (int)e : EML_ELAUNCH;
   }
   return EML_OK;

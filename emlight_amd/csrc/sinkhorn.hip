@@ -28,6 +28,7 @@
 #include "eml_common.h"
 
 #include <cmath>
+#include <type_traits>
 
 // ---- phase timestamps of the cached kernel, experiment builds only (tools/exp_build.sh stamps -DEML_STAMPS, then
 // EML_LIB_PATH=build_exp/lib_stamps.so python tools/sinkhorn_stamps.py): thread 0 of workgroup 1 (sample 0's coupled pair)
@@ -1370,16 +1371,19 @@ int stream_cu_count(hipStream_t stream) {
   return (n < 1 || n > dev_cus) ? dev_cus : n;
 }
 
-// resident workgroups of the split kernel per CU (registers, LDS, wave slots), cached per (instance, device)
-template <typename K>
-int split_occupancy(K kernel, int block, size_t lds, std::atomic<int>* cache) {
+// resident workgroups of a split kernel instance per CU (registers, LDS, wave slots), cached per (instance, device): the
+// instance is a template argument, so the cache is its own
+template <auto Kernel>
+int split_occupancy(int block, size_t lds) {
+  static std::atomic<int> cache[eml::kMaxDevices];
+  EML_ENSURE_LDS(Kernel, lds);
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::atomic<int>& c = cache[dev & (eml::kMaxDevices - 1)];
   int n = c.load(std::memory_order_relaxed);
   if (n == 0) {
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, lds) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, Kernel, block, lds) != hipSuccess) {
       (void)hipGetLastError();
       occ = 0;
     }
@@ -1388,31 +1392,86 @@ int split_occupancy(K kernel, int block, size_t lds, std::atomic<int>* cache) {
   }
   return n > 0 ? n : 0;
 }
-}  // namespace
 
-namespace {
+// One forward call: the name of the entry that was called (for its messages), then EXACTLY the parameters of
+// eml_sinkhorn_fwd_dim_f32 in their order -- the entries fill it positionally (without D, flags or rho: 1, 0, 0.0 and NULL),
+// so a member is added or moved only together with them.  Host side only, never a kernel parameter.
+struct SinkhornCall {
+  const char* who;
+  const float *x, *y, *M, *Mt, *alpha, *beta;
+  double blur, scaling;
+  int p;
+  double diameter;
+  const float* range_lo_hi;
+  float* eps_out;
+  int* n_eps_out;
+  float *diameter_out, *loss, *gx, *gy, *work;
+  int B, N, D, flags;
+  double rho;
+  float* lam_out;
+  hipStream_t stream;
+  double log_blur = 0.0, log_scaling = 0.0;   // f64 like numpy (only log(diameter) is data); set once the call is checked
+};
+
+// The kernel is a template argument, not a function pointer: the static high-water mark inside EML_ENSURE_LDS is then one
+// per kernel instance; behind a pointer all kernels would share it and a later, larger kernel would never be raised.
+template <auto Kernel, class... Args>
+void launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  EML_ENSURE_LDS(Kernel, lds);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+}
+
+// cached / stream kernel: one workgroup pair per sample
+template <auto Kernel>
+void enqueue_loop(const SinkhornCall& c, int block, size_t lds) {
+  launch<Kernel>(dim3(2 * c.B), dim3(block), lds, c.stream, c.x, c.y, c.M, c.Mt, c.alpha, c.beta, c.blur, c.log_blur,
+                 c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
+                 c.work, c.B, c.N, c.D);
+}
+// `only_if`: see the kernel (the rescue launch behind the split kernel)
+template <auto Kernel>
+void enqueue_tiled(const SinkhornCall& c, size_t lds, const int* only_if) {
+  launch<Kernel>(dim3(2 * c.B), dim3(1024), lds, c.stream, c.x, c.y, c.M, c.alpha, c.beta, c.blur, c.log_blur,
+                 c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
+                 c.work, c.B, c.N, only_if, c.D);
+}
+template <auto Kernel>
+void enqueue_split(const SinkhornCall& c, int S, int R, size_t lds, unsigned long long* exch, int* status) {
+  launch<Kernel>(dim3(2 * c.B * S), dim3(16 * R), lds, c.stream, c.x, c.y, c.M, c.alpha, c.beta, c.blur, c.log_blur,
+                 c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
+                 c.work, exch, c.B, S, status, (c.flags & EML_SINKHORN_TEST_STALL) ? 1 : 0);
+}
+
+// LDS-tiled kernel: chord-matrix column tiles (8192 floats, double-buffered) shared by both problems of a workgroup
+template <int kD>
+void launch_tiled(const SinkhornCall& c, const int* only_if) {
+  const int NP = round_up4(c.N) + kJPT;
+  const int lpr = c.N <= 256 ? 2 : 1;
+  const size_t lds = (size_t)((8 + 2 * kD) * NP + 2 * (512 / lpr) * (16 * lpr + 4)) * sizeof(float);
+  if (lpr == 2) enqueue_tiled<sinkhorn_loop_tiled_kernel<2, kD>>(c, lds, only_if);
+  else enqueue_tiled<sinkhorn_loop_tiled_kernel<1, kD>>(c, lds, only_if);
+}
+// Optional: instantiating it here only keeps the kernels' order in the code object as it was (it follows the order in which
+// the host code first names them); nothing at run time depends on it, and a later change may drop this line.
+template void launch_tiled<1>(const SinkhornCall&, const int*);
+
 size_t split_lds_bytes(int N, int R) { return (size_t)(10 * N + R * (N + 32)) * sizeof(float); }
 
-// LDS-tiled kernel: chord-matrix column tiles (8192 floats, double-buffered) shared by both problems of a workgroup.
-// `only_if`: see the kernel (the rescue launch behind the split kernel).
-void launch_tiled(const float* x, const float* y, const float* M, const float* alpha, const float* beta, double blur,
-                  double log_blur, double log_scaling, int p, double diameter, const float* range_lo_hi, float* eps_out,
-                  int* n_eps_out, float* diameter_out, double rho, float* lam_out, float* work, int B, int N,
-                  const int* only_if, hipStream_t stream) {
-  const int NP = round_up4(N) + kJPT;
-  const int lpr = N <= 256 ? 2 : 1;
-  const size_t lds = (size_t)(10 * NP + 2 * (512 / lpr) * (16 * lpr + 4)) * sizeof(float);
-  if (lpr == 2) {
-    EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<2>), lds);
-    hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<2>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
-                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
-                       B, N, only_if, 1);
-  } else {
-    EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<1>), lds);
-    hipLaunchKernelGGL(sinkhorn_loop_tiled_kernel<1>, dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta, blur,
-                       log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out, work,
-                       B, N, only_if, 1);
-  }
+// The instances of the split kernel: f(CPL, R), as two std::integral_constants, for N anchors in S slices (CPL = N / 8
+// columns per lane, R = N / S rows per workgroup).  Asking for the occupancy and launching both go through this table, so
+// that the instance whose occupancy sized the launch is the one launched.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+void with_split_instance(int N, int S, F&& f) {
+  if (N == 256 && S == 8) f(int_c<32>{}, int_c<32>{});
+  else if (N == 256) f(int_c<32>{}, int_c<64>{});
+  else if (N == 192 && S == 8) f(int_c<24>{}, int_c<24>{});
+  else if (N == 192) f(int_c<24>{}, int_c<48>{});
+  else if (N == 320) f(int_c<40>{}, int_c<40>{});
+  else if (N == 384) f(int_c<48>{}, int_c<48>{});
+  else if (N == 448) f(int_c<56>{}, int_c<56>{});
+  else f(int_c<64>{}, int_c<64>{});
 }
 
 // Slices per problem pair for the split kernel, or 0 when the batch does not qualify.  S is sized so that every one of the
@@ -1424,29 +1483,87 @@ int split_slices(int B, int N, int flags, hipStream_t stream) {
   const int dev_cus = device_cu_count();
   if (flags & EML_SINKHORN_FORCE_SPLIT) return (2 * B * 8 <= dev_cus || N > 256) ? 8 : 4;
   const int cus = stream_cu_count(stream);
-  int S = 0;
-  if (2 * B * 8 <= cus) S = 8;
-  else if (N <= 256 && 2 * B * 4 <= cus) S = 4;
+  const int S = 2 * B * 8 <= cus ? 8 : (N <= 256 && 2 * B * 4 <= cus) ? 4 : 0;
   if (S == 0) return 0;
-  const int R = N / S;
-  const size_t lds = split_lds_bytes(N, R);
+  const size_t lds = split_lds_bytes(N, N / S);
   int occ = 0;
-#define EML_SPLIT_OCC(CPLV, RV)                                                                 \
-  do {                                                                                          \
-    static std::atomic<int> cache_[eml::kMaxDevices];                                           \
-    EML_ENSURE_LDS((&sinkhorn_loop_split_kernel<CPLV, RV>), lds);                               \
-    occ = split_occupancy(sinkhorn_loop_split_kernel<CPLV, RV>, 16 * RV, lds, cache_);          \
-  } while (0)
-  if (N == 256 && S == 8) EML_SPLIT_OCC(32, 32);
-  else if (N == 256) EML_SPLIT_OCC(32, 64);
-  else if (N == 192 && S == 8) EML_SPLIT_OCC(24, 24);
-  else if (N == 192) EML_SPLIT_OCC(24, 48);
-  else if (N == 320) EML_SPLIT_OCC(40, 40);
-  else if (N == 384) EML_SPLIT_OCC(48, 48);
-  else if (N == 448) EML_SPLIT_OCC(56, 56);
-  else EML_SPLIT_OCC(64, 64);
-#undef EML_SPLIT_OCC
+  with_split_instance(N, S, [&](auto cpl, auto r) {
+    occ = split_occupancy<sinkhorn_loop_split_kernel<cpl(), r()>>(16 * r(), lds);
+  });
   return ((long)2 * B * S <= (long)occ * cus) ? S : 0;
+}
+
+// Small batch at D = 1: the rows of every problem pair split over S workgroups (one per CU, all resident), duals exchanged
+// through global memory after every sweep (see the kernel).  S = 8 when 16 * B workgroups fit the CUs, else 4.
+int launch_split(const SinkhornCall& c, int S) {
+  const int B = c.B, N = c.N;
+  unsigned long long* exch = reinterpret_cast<unsigned long long*>(c.work + (size_t)8 * B * N);
+  int* status = reinterpret_cast<int*>(c.work + (size_t)24 * B * N);
+  // one memset: the exchange granules and the status words behind them
+  const hipError_t me = hipMemsetAsync(exch, 0, ((size_t)16 * B * N + 4) * sizeof(float), c.stream);
+  if (me != hipSuccess)
+    return eml::fail(EML_ELAUNCH, "%s: memset of the exchange buffer: %s", c.who, hipGetErrorString(me));
+  with_split_instance(N, S, [&](auto cpl, auto r) {
+    enqueue_split<sinkhorn_loop_split_kernel<cpl(), r()>>(c, S, r(), split_lds_bytes(N, r()), exch, status);
+  });
+  if (int rc = eml::check_launch(c.who, "split loop")) return rc;
+  // the rescue: the tiled kernel, gated on the status word -- returns at once unless a slice gave up
+  launch_tiled<1>(c, status);
+  return EML_OK;
+}
+
+// The loop kernel for N (and, at D = 1, for the batch) on kD >= c.D components.  The split kernel is not instantiated for
+// kD > 1: small batches at 192 <= N <= 512 take the tiled kernel there.
+template <int kD>
+int launch_loop(const SinkhornCall& c) {
+  const int B = c.B, N = c.N;
+  const int NP = round_up4(N) + kJPT;
+  int S = 0;
+  if constexpr (kD == 1)
+    if (N <= 512 && (N & 63) == 0 && N >= 192 && !(c.flags & EML_SINKHORN_NO_SPLIT))
+      S = split_slices(B, N, c.flags, c.stream);
+  if (N <= 4 * kCJ) {   // registers; kD > 1: pts [2][kD][NP] + nrm ahead of the D = 1 carve-up, then the chord matrix
+    constexpr int vecs = kD == 1 ? kSmemVecs : kSmemVecs + 2 * kD;
+    enqueue_loop<sinkhorn_loop_kernel<true, kD>>(
+        c, 1024, (size_t)(vecs * NP + N * (round_up4(N) + 4) + kJPT) * sizeof(float));
+  } else if (S > 0) {
+    if (int rc = launch_split(c, S)) return rc;
+  } else if (N <= 512 && (N & 3) == 0) {
+    launch_tiled<kD>(c, nullptr);
+  } else {   // streaming: the same LDS at every kD (the norms take the points' place)
+    enqueue_loop<sinkhorn_loop_kernel<false, kD>>(c, 512, (size_t)(kSmemVecs * NP) * sizeof(float));
+  }
+  return eml::check_launch(c.who, "loop");
+}
+
+template <bool kMultiDim>
+int launch_finish(const SinkhornCall& c) {
+  hipLaunchKernelGGL(sinkhorn_finish_kernel<kMultiDim>, dim3(c.B), dim3(256), 0, c.stream, c.work, c.alpha, c.beta,
+                     c.loss, c.gx, c.gy, c.B, c.N, c.D);
+  return eml::check_launch(c.who, "finish");
+}
+
+// Every forward entry.  rho = reach^p > 0: every softmin of the loop is damped by lam_k = 1 / (1 + eps_k / rho) (the kernels'
+// lam_l); rho <= 0 (and rho = +inf) give lam_k = 1 and the balanced outputs bit for bit.  The finishing kernel is unchanged:
+// the loss reads the damped duals, and the final sweep stores the expectation rows already scaled by lam_last.
+int sinkhorn_forward(SinkhornCall c) {
+  if (std::isnan(c.rho)) return eml::fail(EML_EINVAL, "%s: rho is NaN", c.who);
+  if (!c.x || !c.y || !c.M || !c.Mt || !c.loss || !c.work) return eml::fail(EML_EINVAL, "%s: null pointer", c.who);
+  if (c.flags & ~(EML_SINKHORN_NO_SPLIT | EML_SINKHORN_FORCE_SPLIT | EML_SINKHORN_TEST_STALL))
+    return eml::fail(EML_EINVAL, "%s: unknown flags 0x%x", c.who, c.flags);
+  if (c.B < 0 || c.N < 1 || c.N > 2048) return eml::fail(EML_EINVAL, "%s: need 1<=N<=2048 (got %d)", c.who, c.N);
+  if (!(c.blur > 0.0) || !(c.scaling > 0.0 && c.scaling < 1.0) || c.p < 1)
+    return eml::fail(EML_EINVAL, "%s: need blur>0, 0<scaling<1, p>=1", c.who);
+  if (int rc = refuse_long_schedule(c.who, c.p, c.diameter, c.blur, c.scaling)) return rc;
+  if (c.B == 0) return EML_OK;
+  c.log_blur = std::log(c.blur);
+  c.log_scaling = std::log(c.scaling);
+  if (c.D == 1) {
+    if (int rc = launch_loop<1>(c)) return rc;
+    return launch_finish<false>(c);
+  }
+  if (int rc = c.D == 2 ? launch_loop<2>(c) : c.D <= 4 ? launch_loop<4>(c) : launch_loop<8>(c)) return rc;
+  return launch_finish<true>(c);
 }
 }  // namespace
 
@@ -1455,8 +1572,9 @@ extern "C" int eml_sinkhorn_fwd_f32(const float* x, const float* y, const float*
                                     double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
                                     float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                                     eml_stream_t stream) {
-  return eml_sinkhorn_fwd_ex_f32(x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                                 diameter_out, loss, gx, gy, work, B, N, 0, stream);
+  return sinkhorn_forward({"eml_sinkhorn_fwd_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
+                           eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, 1, 0, 0.0, nullptr,
+                           (hipStream_t)stream});
 }
 
 extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const float* M, const float* Mt,
@@ -1464,84 +1582,19 @@ extern "C" int eml_sinkhorn_fwd_ex_f32(const float* x, const float* y, const flo
                                        double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
                                        float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                                        int flags, eml_stream_t stream) {
-  return eml_sinkhorn_fwd_rho_f32(x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                                  diameter_out, loss, gx, gy, work, B, N, flags, 0.0, nullptr, stream);
+  return sinkhorn_forward({"eml_sinkhorn_fwd_ex_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
+                           eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, 1, flags, 0.0, nullptr,
+                           (hipStream_t)stream});
 }
 
-// rho = reach^p > 0: every softmin of the loop is damped by lam_k = 1 / (1 + eps_k / rho) (the kernels' lam_l); rho <= 0
-// (and rho = +inf) give lam_k = 1 and the balanced outputs bit for bit.  The finishing kernel is unchanged: the loss reads
-// the damped duals, and the final sweep stores the expectation rows already scaled by lam_last.
 extern "C" int eml_sinkhorn_fwd_rho_f32(const float* x, const float* y, const float* M, const float* Mt,
                                         const float* alpha, const float* beta, double blur, double scaling, int p,
                                         double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
                                         float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                                         int flags, double rho, float* lam_out, eml_stream_t stream) {
-  if (std::isnan(rho)) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_rho_f32: rho is NaN");
-  if (!x || !y || !M || !Mt || !loss || !work) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: null pointer");
-  if (flags & ~(EML_SINKHORN_NO_SPLIT | EML_SINKHORN_FORCE_SPLIT | EML_SINKHORN_TEST_STALL))
-    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_ex_f32: unknown flags 0x%x", flags);
-  if (B < 0 || N < 1 || N > 2048) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: need 1<=N<=2048 (got %d)", N);
-  if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
-    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_f32: need blur>0, 0<scaling<1, p>=1");
-  if (int rc = refuse_long_schedule("eml_sinkhorn_fwd_f32", p, diameter, blur, scaling)) return rc;
-  if (B == 0) return EML_OK;
-  const double log_blur = std::log(blur), log_scaling = std::log(scaling);   // f64 like numpy; only log(diameter) is data
-  const int NP = round_up4(N) + kJPT;
-  size_t lds = (size_t)(kSmemVecs * NP) * sizeof(float);
-  int split_s = 0;
-  if (N <= 4 * kCJ) {
-    lds += (size_t)(N * (round_up4(N) + 4) + kJPT) * sizeof(float);
-    EML_ENSURE_LDS((&sinkhorn_loop_kernel<true>), lds);
-    hipLaunchKernelGGL(sinkhorn_loop_kernel<true>, dim3(2 * B), dim3(1024), lds, (hipStream_t)stream, x, y, M, Mt,
-                       alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       rho, lam_out, work, B, N, 1);
-  } else if (N <= 512 && (N & 63) == 0 && N >= 192 && !(flags & EML_SINKHORN_NO_SPLIT) &&
-             (split_s = split_slices(B, N, flags, (hipStream_t)stream)) > 0) {
-    // small batch: the rows of every problem pair split over S workgroups (one per CU, all resident), duals exchanged
-    // through global memory after every sweep (see the kernel).  S = 8 when 16 * B workgroups fit the CUs, else 4.
-    const int S = split_s;
-    const int R = N / S;
-    unsigned long long* exch = reinterpret_cast<unsigned long long*>(work + (size_t)8 * B * N);
-    int* status = reinterpret_cast<int*>(work + (size_t)24 * B * N);
-    // one memset: the exchange granules and the status words behind them
-    hipError_t me = hipMemsetAsync(exch, 0, ((size_t)16 * B * N + 4) * sizeof(float), (hipStream_t)stream);
-    if (me != hipSuccess) return eml::fail(EML_ELAUNCH, "eml_sinkhorn_fwd_f32: memset of the exchange buffer: %s", hipGetErrorString(me));
-    lds = split_lds_bytes(N, R);
-#define EML_LAUNCH_SPLIT(CPLV, RV)                                                                                     \
-  do {                                                                                                                 \
-    EML_ENSURE_LDS((&sinkhorn_loop_split_kernel<CPLV, RV>), lds);                                                      \
-    hipLaunchKernelGGL((sinkhorn_loop_split_kernel<CPLV, RV>), dim3(2 * B * S), dim3(16 * RV), lds, (hipStream_t)stream, \
-                       x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, \
-                       diameter_out, rho, lam_out, work, exch, B, S, status, (flags & EML_SINKHORN_TEST_STALL) ? 1 : 0); \
-  } while (0)
-    if (N == 256 && S == 8) EML_LAUNCH_SPLIT(32, 32);
-    else if (N == 256) EML_LAUNCH_SPLIT(32, 64);
-    else if (N == 192 && S == 8) EML_LAUNCH_SPLIT(24, 24);
-    else if (N == 192) EML_LAUNCH_SPLIT(24, 48);
-    else if (N == 320) EML_LAUNCH_SPLIT(40, 40);
-    else if (N == 384) EML_LAUNCH_SPLIT(48, 48);
-    else if (N == 448) EML_LAUNCH_SPLIT(56, 56);
-    else EML_LAUNCH_SPLIT(64, 64);
-#undef EML_LAUNCH_SPLIT
-    int rcs = eml::check_launch("eml_sinkhorn_fwd_f32(split loop)");
-    if (rcs) return rcs;
-    // the rescue: the tiled kernel, gated on the status word -- returns at once unless a slice gave up
-    launch_tiled(x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                 diameter_out, rho, lam_out, work, B, N, status, (hipStream_t)stream);
-  } else if (N <= 512 && (N & 3) == 0) {
-    launch_tiled(x, y, M, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                 diameter_out, rho, lam_out, work, B, N, nullptr, (hipStream_t)stream);
-  } else {
-    EML_ENSURE_LDS((&sinkhorn_loop_kernel<false>), lds);
-    hipLaunchKernelGGL(sinkhorn_loop_kernel<false>, dim3(2 * B), dim3(512), lds, (hipStream_t)stream, x, y, M, Mt,
-                       alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out,
-                       rho, lam_out, work, B, N, 1);
-  }
-  int rc = eml::check_launch("eml_sinkhorn_fwd_f32(loop)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(sinkhorn_finish_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, work, alpha, beta, loss,
-                     gx, gy, B, N, 1);
-  return eml::check_launch("eml_sinkhorn_fwd_f32(finish)");
+  return sinkhorn_forward({"eml_sinkhorn_fwd_rho_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
+                           eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, 1, flags, rho, lam_out,
+                           (hipStream_t)stream});
 }
 
 extern "C" int eml_sinkhorn_bwd_f32(const float* gloss, const float* gunit, float* gout, int B, int N,
@@ -1554,8 +1607,8 @@ extern "C" int eml_sinkhorn_bwd_f32(const float* gloss, const float* gunit, floa
   return eml::check_launch("eml_sinkhorn_bwd_f32");
 }
 
-// ---- D-dimensional points (SamplesLoss on (B,N,D) samples, 1 <= D <= EML_SINKHORN_MAX_DIM).  D = 1 forwards to the
-// entries above unchanged.  D > 1 runs the loop kernels instantiated for kD = 2, 4 or 8 components (the smallest that
+// ---- D-dimensional points (SamplesLoss on (B,N,D) samples, 1 <= D <= EML_SINKHORN_MAX_DIM).  D = 1 runs what the
+// entries above run.  D > 1 runs the loop kernels instantiated for kD = 2, 4 or 8 components (the smallest that
 // holds D; the components past D are zero and add nothing); the split kernel is not instantiated for it: small batches at
 // 192 <= N <= 512 take the tiled kernel.
 extern "C" size_t eml_sinkhorn_dim_work_floats(int B, int N, int D) {
@@ -1583,44 +1636,6 @@ extern "C" int eml_sinkhorn_schedule_dim_f32(const float* x, const float* y, lon
   return eml::check_launch("eml_sinkhorn_schedule_dim_f32");
 }
 
-namespace {
-template <int kD>
-int launch_loop_dim(const float* x, const float* y, const float* M, const float* Mt, const float* alpha,
-                    const float* beta, double blur, double log_blur, double log_scaling, int p, double diameter,
-                    const float* range_lo_hi, float* eps_out, int* n_eps_out, float* diameter_out, double rho,
-                    float* lam_out, float* work, int B, int N, int D, hipStream_t stream) {
-  const int NP = round_up4(N) + kJPT;
-  if (N <= 4 * kCJ) {   // registers: pts [2][kD][NP] + nrm ahead of the D = 1 carve-up, then the chord matrix
-    const size_t lds = (size_t)((kSmemVecs + 2 * kD) * NP + N * (round_up4(N) + 4) + kJPT) * sizeof(float);
-    EML_ENSURE_LDS((&sinkhorn_loop_kernel<true, kD>), lds);
-    hipLaunchKernelGGL((sinkhorn_loop_kernel<true, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, Mt, alpha, beta,
-                       blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out,
-                       work, B, N, D);
-  } else if (N <= 512 && (N & 3) == 0) {   // LDS tiles (also the small batches the split kernel takes at D = 1)
-    const int lpr = N <= 256 ? 2 : 1;
-    const size_t lds = (size_t)((8 + 2 * kD) * NP + 2 * (512 / lpr) * (16 * lpr + 4)) * sizeof(float);
-    if (lpr == 2) {
-      EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<2, kD>), lds);
-      hipLaunchKernelGGL((sinkhorn_loop_tiled_kernel<2, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta,
-                         blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho,
-                         lam_out, work, B, N, nullptr, D);
-    } else {
-      EML_ENSURE_LDS((&sinkhorn_loop_tiled_kernel<1, kD>), lds);
-      hipLaunchKernelGGL((sinkhorn_loop_tiled_kernel<1, kD>), dim3(2 * B), dim3(1024), lds, stream, x, y, M, alpha, beta,
-                         blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho,
-                         lam_out, work, B, N, nullptr, D);
-    }
-  } else {   // streaming: the same LDS as D = 1 (the norms take the points' place)
-    const size_t lds = (size_t)(kSmemVecs * NP) * sizeof(float);
-    EML_ENSURE_LDS((&sinkhorn_loop_kernel<false, kD>), lds);
-    hipLaunchKernelGGL((sinkhorn_loop_kernel<false, kD>), dim3(2 * B), dim3(512), lds, stream, x, y, M, Mt, alpha, beta,
-                       blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out, n_eps_out, diameter_out, rho, lam_out,
-                       work, B, N, D);
-  }
-  return eml::check_launch("eml_sinkhorn_fwd_dim_f32(loop)");
-}
-}  // namespace
-
 extern "C" int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const float* M, const float* Mt,
                                         const float* alpha, const float* beta, double blur, double scaling, int p,
                                         double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
@@ -1628,33 +1643,9 @@ extern "C" int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const fl
                                         int D, int flags, double rho, float* lam_out, eml_stream_t stream) {
   if (D < 1 || D > EML_SINKHORN_MAX_DIM)
     return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need 1 <= D <= %d (got %d)", EML_SINKHORN_MAX_DIM, D);
-  if (D == 1)
-    return eml_sinkhorn_fwd_rho_f32(x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi, eps_out, n_eps_out,
-                                    diameter_out, loss, gx, gy, work, B, N, flags, rho, lam_out, stream);
-  if (std::isnan(rho)) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: rho is NaN");
-  if (!x || !y || !M || !Mt || !loss || !work) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: null pointer");
-  if (flags & ~(EML_SINKHORN_NO_SPLIT | EML_SINKHORN_FORCE_SPLIT | EML_SINKHORN_TEST_STALL))
-    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: unknown flags 0x%x", flags);
-  if (B < 0 || N < 1 || N > 2048) return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need 1<=N<=2048 (got %d)", N);
-  if (!(blur > 0.0) || !(scaling > 0.0 && scaling < 1.0) || p < 1)
-    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_dim_f32: need blur>0, 0<scaling<1, p>=1");
-  if (int rc = refuse_long_schedule("eml_sinkhorn_fwd_dim_f32", p, diameter, blur, scaling)) return rc;
-  if (B == 0) return EML_OK;
-  const double log_blur = std::log(blur), log_scaling = std::log(scaling);
-  const hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (D <= 2)
-    rc = launch_loop_dim<2>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
-                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
-  else if (D <= 4)
-    rc = launch_loop_dim<4>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
-                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
-  else
-    rc = launch_loop_dim<8>(x, y, M, Mt, alpha, beta, blur, log_blur, log_scaling, p, diameter, range_lo_hi, eps_out,
-                            n_eps_out, diameter_out, rho, lam_out, work, B, N, D, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(sinkhorn_finish_kernel<true>, dim3(B), dim3(256), 0, s, work, alpha, beta, loss, gx, gy, B, N, D);
-  return eml::check_launch("eml_sinkhorn_fwd_dim_f32(finish)");
+  return sinkhorn_forward({"eml_sinkhorn_fwd_dim_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
+                           eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, D, flags, rho, lam_out,
+                           (hipStream_t)stream});
 }
 
 extern "C" int eml_sinkhorn_bwd_weights_f32(const float* gloss, const float* work, float* galpha, float* gbeta, int B,
