@@ -2,6 +2,8 @@
 numpy float64.  A helper of ``test_gpu_needlets.py`` / ``test_needlets_abi.py``, not a test.  Nothing here looks at the
 product code: HEALPix comes from the pixel-index formulae (Gorski et al. 2005, eqs. 2-9) rather than ring by ring, and the
 zonal sum is numpy's Clenshaw ``legval`` rather than the kernels' forward recurrence."""
+import functools
+
 import numpy as np
 from numpy.polynomial import legendre
 
@@ -165,33 +167,109 @@ def hdr_image(B, H, W, seed=0):
     return (g.random((B, 3, H, W)) ** 4 * 50.0 + 0.01).astype(np.float32)
 
 
+# ------------------------------------------------------------------------------------------------ the GPU tests' inputs
+# The cases of test_gpu_needlets.py, kept here so that the floors below are measured on exactly the arrays the tests feed in
+# (hdr_image seeds itself with B, so another batch size is another image).  A case is (H, W, jmax, B).
+GOLDEN_SHAPES = [(12, 24, 1), (12, 24, 2), (16, 32, 3)]                    # images and coefficients of the golden file (B = 2)
+GRID_SHAPES = [(12, 24, 1), (16, 32, 3), (32, 64, 2), (4, 8, 0)]           # the matrix on both grids
+# analysis with more than one chunk per split (make_plan: per >= 2): K, chunks, per, splits, chunks in the last split, tail
+#   25 x 47 jmax 4: 4093, 19, 2, 10, 1, 23      50 x 100 jmax 1: 61, 79, 2, 40, 1, 8      48 x 96 jmax 0: 13, 72, 2, 36, 2, 64
+PER2_SHAPES = [(25, 47, 4), (50, 100, 1), (48, 96, 0)]
+ONE_CHUNK_SHAPES = [(4, 8, 0), (3, 5, 2)]                                  # P < 64: a single ragged chunk
+ANALYSIS_CASES = [(12, 24, 1, 2), (16, 32, 3, 1), (32, 64, 2, 11),
+                  (25, 47, 4, 2), (50, 100, 1, 2), (48, 96, 0, 1), (4, 8, 0, 3), (3, 5, 2, 2)]
+SYNTHESIS_CASES = [(12, 24, 1, 1), (16, 32, 3, 11), (32, 64, 2, 2),
+                   (25, 47, 4, 2), (4, 8, 0, 3), (3, 5, 2, 2), (48, 96, 0, 1)]
+COLUMN_GROUP_CASES = [(12, 24, 1, 32), (12, 24, 1, 33), (12, 24, 1, 65)]   # 3B = 96, 96 + 3, 96 + 96 + 3 planes
+ADJOINT_CASES = [(12, 24, 1, 2), (16, 32, 3, 2), (25, 47, 4, 2), (50, 100, 1, 33)]
+ADJOINT_SEEDS = {"x": 1, "g": 2, "up": 3}                                  # the panorama, the coefficients, the upstream image
+SUM_BACKWARD_CASE = (12, 24, 1, 2)                                         # gradients of .sum(): all-ones upstream
+
+
+def floor_key(H, W, jmax, B, source=0):
+    """The name of a floor.  ``source``: the seed of ``hdr_image`` (0 is not written), "golden" or "ones"."""
+    if isinstance(source, str):
+        tail = "_" + source
+    elif source == 0:
+        tail = ""
+    else:
+        tail = "_s%d" % source
+    return "%dx%d_j%d_b%d%s" % (H, W, jmax, B, tail)
+
+
+def floor_cases():
+    """{"analysis": [(H, W, jmax, B, source)], "synthesis": [...]}: every input a GPU test holds against an analysis or a
+    synthesis tolerance."""
+    ana = [(H, W, j, 2, "golden") for H, W, j in GOLDEN_SHAPES] + [c + (0,) for c in ANALYSIS_CASES + COLUMN_GROUP_CASES]
+    syn = [c + (0,) for c in SYNTHESIS_CASES + COLUMN_GROUP_CASES]
+    for c in ADJOINT_CASES:
+        ana += [c + (ADJOINT_SEEDS["x"],), c + (ADJOINT_SEEDS["up"],)]
+        syn += [c + (ADJOINT_SEEDS["g"],)]
+    ana.append(SUM_BACKWARD_CASE + ("ones",))
+    syn.append(SUM_BACKWARD_CASE + ("ones",))
+    return {"analysis": ana, "synthesis": syn}
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_matrices(H, W, jmax):
+    """(M32, M64) on the reference grid: the float32 restatement and the float64 definition."""
+    th, ph = grid_angles(H, W)
+    return matrix_f32(th, ph, jmax), matrix(th, ph, jmax)
+
+
+def analysis_floor(im, H, W, jmax, want=None):
+    """The float32 restatement's weighted analysis of ``im`` (B, 3, H, W) on the reference grid against ``want`` (default:
+    the float64 analysis of the same image), as max|error| / max|value|."""
+    f = np.float32
+    M32, M64 = _grid_matrices(H, W, jmax)
+    B = im.shape[0]
+    if want is None:
+        want = analysis(im, M64, solid_angles(H, W))
+    flat = np.asarray(im, dtype=f).reshape(3 * B, H * W) * solid_angles(H, W).astype(f)
+    got = np.stack([np.sum(M32 * flat[n][:, None], axis=0, dtype=f) for n in range(3 * B)]).reshape(B, 3, -1).transpose(0, 2, 1)
+    return rel_err(got, want)
+
+
+def synthesis_floor(co, H, W, jmax):
+    """The float32 restatement's (unweighted) synthesis of float32 coefficients ``co`` (B, K, 3) against the float64 one."""
+    f = np.float32
+    M32, M64 = _grid_matrices(H, W, jmax)
+    B = co.shape[0]
+    rec = np.stack([np.sum(M32 * co[b, :, c][None, :], axis=1, dtype=f) for b in range(B) for c in range(3)])
+    return rel_err(rec, synthesis(co, M64, H, W).reshape(3 * B, -1))
+
+
 def float32_floors(golden):
     """The float32 floors behind the GPU tolerances (test_gpu_needlets.py): what the kernels' arithmetic reaches in numpy
     float32 -- float32 directions, centres, table and solid angles, every product and (pairwise) sum rounded to float32 --
-    as max|error| / max|value|.  The error of P_l(t) for a float32 t grows with l^2, hence one floor per jmax or shape:
-    * matrix[jmax]: against the reference-made golden (a);
-    * analysis["HxW_jJ"]: against golden (c); at 32 x 64 (not in the golden file) against this file's float64;
-    * synthesis["HxW_jJ"]: of the same coefficients, against this file's float64 (the reference writes no reconstruction)."""
+    as max|error| / max|value|.  The error of P_l(t) for a float32 t grows with l^2 and a sum's error depends on its terms,
+    hence one floor per jmax (matrix) or per input (analysis, synthesis; ``floor_cases`` lists them, ``floor_key`` names them):
+    * matrix[jmax]: against the reference-made golden (a); jmax 0 is not in that file: the same points, against this file's
+      float64, which equals the golden to 1e-9 where they overlap;
+    * analysis[key]: the golden image against golden (c); every other image against this file's float64;
+    * synthesis[key]: of the float32-rounded float64 coefficients of that image, against this file's float64 (the reference
+      writes no reconstruction).
+    "ones" is the all-ones panorama, and the all-ones coefficients: the upstream gradient of a ``.sum()``."""
     f = np.float32
     floors = {"matrix": {}, "analysis": {}, "synthesis": {}}
+    th, ph = golden["a/j1/theta"], golden["a/j1/phi"]
+    floors["matrix"][0] = rel_err(matrix_f32(th, ph, 0), matrix(th, ph, 0))
     for jmax in (1, 2, 3, 4):
         th, ph = golden["a/j%d/theta" % jmax], golden["a/j%d/phi" % jmax]
         floors["matrix"][jmax] = rel_err(matrix_f32(th, ph, jmax), golden["a/j%d/matrix" % jmax])
-    for H, W, jmax in ((12, 24, 1), (12, 24, 2), (16, 32, 3), (32, 64, 2)):
-        key = "%dx%d_j%d" % (H, W, jmax)
-        th, ph = grid_angles(H, W)
-        M32, w32, M64 = matrix_f32(th, ph, jmax), solid_angles(H, W).astype(f), matrix(th, ph, jmax)
-        if "c/%s/image" % key in golden:
-            im, want = golden["c/%s/image" % key], golden["c/%s/coeffs" % key]
+    for H, W, jmax, B, source in floor_cases()["analysis"]:
+        if source == "golden":
+            name = "%dx%d_j%d" % (H, W, jmax)
+            im, want = golden["c/%s/image" % name], golden["c/%s/coeffs" % name]
         else:
-            im = hdr_image(2, H, W)
-            want = analysis(im, M64, solid_angles(H, W))
-        flat = (im.reshape(6, H * W) * w32)
-        got = np.stack([np.sum(M32 * flat[n][:, None], axis=0, dtype=f) for n in range(6)]).reshape(2, 3, -1).transpose(0, 2, 1)
-        floors["analysis"][key] = rel_err(got, want)
-        co = want.astype(f)
-        rec = np.stack([np.sum(M32 * co[b, :, c][None, :], axis=1, dtype=f) for b in range(2) for c in range(3)])
-        floors["synthesis"][key] = rel_err(rec, synthesis(co, M64, H, W).reshape(6, -1))
+            im, want = np.ones((B, 3, H, W), dtype=f) if source == "ones" else hdr_image(B, H, W, source), None
+        floors["analysis"][floor_key(H, W, jmax, B, source)] = analysis_floor(im, H, W, jmax, want)
+    for H, W, jmax, B, source in floor_cases()["synthesis"]:
+        if source == "ones":
+            co = np.ones((B, rows(jmax), 3), dtype=f)
+        else:
+            co = analysis(hdr_image(B, H, W, source), _grid_matrices(H, W, jmax)[1], solid_angles(H, W)).astype(f)
+        floors["synthesis"][floor_key(H, W, jmax, B, source)] = synthesis_floor(co, H, W, jmax)
     return floors
 
 

@@ -257,6 +257,35 @@ def test_launcher_argument_validation_without_gpu(built_lib):
     assert wf(128 * 256, 3, 5) == 5 * wf(128 * 256, 3, 1) == 5 * 64 * 1021 * 3
 
 
+def test_the_gpu_cases_reach_the_chunk_loop_of_the_analysis(built_lib):
+    """The analysis stages 64 pixels per chunk and gives each split ``per`` chunks.  Only with ``per >= 2`` does the kernel's
+    chunk loop come round again (the prefetch of the next chunk, the barrier before the staging buffer is overwritten, a last
+    split that is clipped).  The plan is not exported, its scratch size is: ``work_floats(P, jmax, 1) = splits * K * 3``, and
+    ``per >= 2`` exactly when there are fewer splits than chunks.  If the plan's constants move, this says that the GPU cases
+    of ``test_gpu_needlets.py`` no longer cover the loop."""
+    wf = built_lib.eml_needlet_work_floats
+
+    def splits_and_chunks(H, W, jmax):
+        floats = wf(H * W, jmax, 1)
+        assert floats > 0 and floats % (3 * KS[jmax]) == 0, (H, W, jmax, floats)
+        return floats // (3 * KS[jmax]), -(-H * W // 64)
+
+    assert oracle.PER2_SHAPES == [(25, 47, 4), (50, 100, 1), (48, 96, 0)]
+    assert [splits_and_chunks(*c) for c in oracle.PER2_SHAPES] == [(10, 19), (40, 79), (36, 72)]      # each < its chunk count
+    for H, W, jmax in oracle.PER2_SHAPES:
+        assert (H, W, jmax) in {c[:3] for c in oracle.ANALYSIS_CASES}, "a per >= 2 shape no analysis test runs"
+        splits, chunks = splits_and_chunks(H, W, jmax)
+        assert splits < chunks, (H, W, jmax, splits, chunks)
+    assert {c[:3] for c in oracle.ADJOINT_CASES} >= set(oracle.PER2_SHAPES[:2])
+    one_chunk_per_split = [(12, 24, 1), (12, 24, 2), (16, 32, 3), (32, 64, 2)] + oracle.ONE_CHUNK_SHAPES
+    for H, W, jmax in one_chunk_per_split:
+        splits, chunks = splits_and_chunks(H, W, jmax)
+        assert splits == chunks, (H, W, jmax, splits, chunks)
+    assert [splits_and_chunks(*c)[1] for c in oracle.ONE_CHUNK_SHAPES] == [1, 1]
+    every = {c[:3] for c in oracle.ANALYSIS_CASES + oracle.COLUMN_GROUP_CASES + oracle.ADJOINT_CASES} | set(oracle.GOLDEN_SHAPES)
+    assert every == set(oracle.PER2_SHAPES) | set(one_chunk_per_split), "a shape of the GPU file this test does not classify"
+
+
 # ------------------------------------------------------------------------------------------------ the definition
 def test_oracle_equals_the_reference_made_golden(golden):
     for jmax in (1, 2, 3, 4):
@@ -387,9 +416,14 @@ def test_command_line_on_host_stand_ins(tmp_path, monkeypatch, capsys):
 
 
 def test_the_gpu_tolerances_are_the_measured_float32_floors(golden):
-    """``FLOOR`` of test_gpu_needlets.py is what the float32 restatement of the kernels' arithmetic reaches here, rounded up."""
+    """``FLOOR`` of test_gpu_needlets.py is what the float32 restatement of the kernels' arithmetic reaches here, rounded up:
+    one floor for every input the GPU file holds against an analysis or a synthesis tolerance, measured on that input."""
     from tests.test_gpu_needlets import FLOOR, MARGIN
     measured = oracle.float32_floors(golden)
+    cases = oracle.floor_cases()
+    assert all(len(set(v)) == len(v) for v in cases.values())
+    assert {q: set(FLOOR[q]) for q in cases} == {q: {oracle.floor_key(*c) for c in v} for q, v in cases.items()}
+    assert set(FLOOR["matrix"]) == {0, 1, 2, 3, 4}
     assert MARGIN == 4.0 and {q: set(v) for q, v in FLOOR.items()} == {q: set(v) for q, v in measured.items()}
     for q, table in measured.items():
         for k, v in table.items():
