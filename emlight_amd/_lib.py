@@ -80,6 +80,11 @@ SIGNATURES = {
     "eml_needlet_analysis_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _f32p, _f32p, _int, _f32p, _f32p, _stream]),
     "eml_needlet_synthesis_f32": (_int, [_f32p, _f32p, _f32p, _int, _int, _f32p, _f32p, _int, _f32p, _stream]),
     "eml_needlet_sparsify_f32": (_int, [_f32p, _int, _int, _int, ctypes.c_double, _f32p, _i32p, _stream]),
+    # real spherical harmonics: basis matrix, separable analysis / synthesis on the grid (each the other's adjoint)
+    "eml_sh_basis_f32": (_int, [_f32p, _int, _f32p, _int, _f32p, _stream]),
+    "eml_sh_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int]),
+    "eml_sh_analysis_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _f32p, _f32p, _stream]),
+    "eml_sh_synthesis_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _f32p, _stream]),
     # GenProjector SphereConv2D
     "eml_sphere_tap_table_f32": (_int, [_f32p, _int, _int, _int, _int, _i32p, _f32p, _stream]),
     "eml_sphere_im2col_f32": (_int, [_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),

@@ -74,6 +74,12 @@ def cubature(jmax):
     return np.concatenate([healpix_ring_centres(2 ** j) for j in range(_jmax(jmax) + 1)], 0)
 
 
+def cubature_weights(jmax):
+    """``lambda_j = 4 pi / Npix_j`` for the levels 0..jmax, ``(jmax + 1,)`` float64: the equal weight of a level's centres
+    (``sphere_needlets.py:50-52``)."""
+    return np.array([4.0 * np.pi / (12.0 * 4 ** j) for j in range(_jmax(jmax) + 1)])
+
+
 def antipodal_pairs(jmax):
     """``(cubature_pair, cubature_use)`` of ``spneedlet_pair`` (``sphere_needlets.py:107-128``) as int64 arrays over the
     stacked centres: ``cubature()[pair[i]] == -cubature()[i]``, and ``use`` lists the ``i`` with ``pair[i] > i`` -- the
@@ -135,8 +141,9 @@ def coefficient_table(jmax):
     out = np.zeros((jmax + 2, TABLE_ROW))
     out[0, 0] = 1.0 / np.sqrt(4.0 * np.pi)
     l = np.arange(b.shape[1])
+    lam = cubature_weights(jmax)
     for j in range(jmax + 1):
-        out[j + 1, :b.shape[1]] = np.sqrt(4.0 * np.pi / (12.0 * 4 ** j)) * b[j] * (2.0 * l + 1.0) / (4.0 * np.pi)
+        out[j + 1, :b.shape[1]] = np.sqrt(lam[j]) * b[j] * (2.0 * l + 1.0) / (4.0 * np.pi)
     return out
 
 
@@ -317,32 +324,40 @@ def _batcher(fov, device):
     return PanoramaBatcher(fov_deg=fov, device=device)
 
 
-def coefficients_of_directory(pano_dir, out_dir, jmax=3, height=128, fov=60.0, alpha=True, sparsify=None, batch_size=8,
-                              device="cuda:0"):
-    """``gt_gen_j3.py`` over ``pano_dir/*.npy``: area-resize to ``height x 2 height`` (``:31``), multiply by the tonemap alpha
-    of the crop at azimuth 0 (``:34-37``) unless ``alpha`` is false, project (``:39-43``), optionally threshold levels 2 and 3
-    (``mat_gen2.py:43-51``), write ``out_dir/<name>.npy`` ``(K, 3)`` float32 (``:45``).  Returns the names written."""
+def prepared_batches(pano_dir, height, width, fov=60.0, alpha=True, batch_size=8, device="cuda:0"):
+    """The input side of ``gt_gen_j3.py`` over ``pano_dir/*.npy``: yields ``(names, x)`` per batch, ``x`` ``(B, 3, height,
+    width)`` contiguous -- the panoramas area-resized (``:31``) and, unless ``alpha`` is false, multiplied by the tonemap
+    alpha of the crop at azimuth 0 (``:34-37``)."""
     from torch.utils.data import DataLoader
     from .RegressionNetwork.data import PanoramaDataset
-    basis = NeedletBasis(jmax=jmax, height=height, width=2 * height, device=device)
-    levels = tuple(v for v in (2, 3) if v <= basis.jmax)
-    if sparsify is not None and not levels:
-        raise ValueError("--sparsify thresholds levels 2 and 3; jmax = %d has neither" % basis.jmax)
     loader = DataLoader(PanoramaDataset(pano_dir), batch_size=batch_size, shuffle=False, drop_last=False)
     batcher = _batcher(fov, device)
-    batcher.PANO_HW = (basis.height, basis.width)
-    os.makedirs(out_dir, exist_ok=True)
-    names = []
+    batcher.PANO_HW = (height, width)
     for para in loader:
         panos = para["pano"].to(device)
         x = batcher.small(panos, 0.0).permute(0, 3, 1, 2)
         if alpha:
             x = x * batcher.tone(batcher.crop(panos, 0.0, fov))[1].reshape(-1, 1, 1, 1)
-        coeffs = basis.analysis(x.contiguous())
+        yield list(para["name"]), x.contiguous()
+
+
+def coefficients_of_directory(pano_dir, out_dir, jmax=3, height=128, fov=60.0, alpha=True, sparsify=None, batch_size=8,
+                              device="cuda:0"):
+    """``gt_gen_j3.py`` over ``pano_dir/*.npy``: area-resize to ``height x 2 height`` (``:31``), multiply by the tonemap alpha
+    of the crop at azimuth 0 (``:34-37``) unless ``alpha`` is false, project (``:39-43``), optionally threshold levels 2 and 3
+    (``mat_gen2.py:43-51``), write ``out_dir/<name>.npy`` ``(K, 3)`` float32 (``:45``).  Returns the names written."""
+    basis = NeedletBasis(jmax=jmax, height=height, width=2 * height, device=device)
+    levels = tuple(v for v in (2, 3) if v <= basis.jmax)
+    if sparsify is not None and not levels:
+        raise ValueError("--sparsify thresholds levels 2 and 3; jmax = %d has neither" % basis.jmax)
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for batch_names, x in prepared_batches(pano_dir, basis.height, basis.width, fov, alpha, batch_size, device):
+        coeffs = basis.analysis(x)
         if sparsify is not None:
             coeffs = basis.sparsify(coeffs, ratio=sparsify, levels=levels)[0]
         host = coeffs.cpu().numpy()
-        for q, name in enumerate(para["name"]):
+        for q, name in enumerate(batch_names):
             np.save(os.path.join(out_dir, name + ".npy"), host[q])
             names.append(name)
     return names

@@ -983,6 +983,36 @@ int eml_needlet_synthesis_f32(const float* coeffs, const float* dirs, const floa
 int eml_needlet_sparsify_f32(const float* coeffs, int B, int jmax, int levels_mask, double ratio, float* out, int* kept,
                              eml_stream_t stream);
 
+/* ---------------------------------------------------------------- real spherical harmonics (Needlets/sphere_harmonics.py)
+ * K = (lmax+1)^2 columns, column l^2 + l + m (shIndex, sphere_harmonics.py:7-8), 0 <= lmax <= 32.  With Ybar_l^m the fully
+ * normalised associated Legendre function (Condon-Shortley phase) a column is scale * Ybar_l^|m|(cos theta) {cos, sin}(|m| phi);
+ * which part a column takes and its signed scale is the convention: shEvaluate / SH (:48-70: m > 0 sqrt(2) cos, m < 0 sqrt(2)
+ * sin) or spharmonic (:94-115: m < 0 sqrt(2) cos, m > 0 (-1)^m sqrt(2) sin).  DESIGN.md section 17.
+ * Tables, f32 on the device, made by the caller in f64:
+ *   tab (2343): d[33], a[33][33], b[33][33] (both [m][l]) of the recurrence q_m = d_m, q_l = a_lm (z q_{l-1} - b_lm q_{l-2})
+ *     for Ybar_l^m / sin^m theta, then conv[33][4] = per order m {+1: the cos part is column +m and the sin part -m, -1: the
+ *     other way round; scale of the cos part; scale of the sin part; 0};
+ *   rows (H,2) = cos theta_y, sin theta_y;  weights (H) per image row or NULL (= 1);
+ *   fourier (W,33,2) = cos(m phi_x), sin(m phi_x) for m = 0..32 whatever lmax.
+ * 1 <= P = H * W <= 2^24, B <= 65535; B == 0 returns 0 and launches nothing.  The four entry points of this section are
+ * additions within ABI 31 (no existing signature changed; the binding refuses a library without them by name). */
+/* out (P,K) = Y_k(x_p) at unit vectors dirs (P,3): spharmonic (sphere_harmonics.py:94-115) / shEvaluate (:60-70).  One
+ * recurrence per (point, m). */
+int eml_sh_basis_f32(const float* dirs, int P, const float* tab, int lmax, float* out, eml_stream_t stream);
+/* pano (B,3,H,W) -> coeffs (B,K,3) = sum_p Y_k(x_p) weights[y] pano[b,c,p] on the product grid (the `np.sum(im * SH_matrix *
+ * solidAngle)` of the SH baselines, with spharmonic, sphere_harmonics.py:94): per image row the 2 lmax + 1 Fourier sums, then
+ * times weights[y] Ybar_l^m(z_y) and summed over the rows; no (P,K) operand exists.  Row blocks of 8 write partial coefficients
+ * to `work` (eml_sh_work_floats(H, W, lmax, B) floats; 0 for sizes the launcher refuses) and a second launch adds them in block
+ * order: no atomics, run-to-run exact, independent of the batch.  Also the gradient of eml_sh_synthesis_f32 w.r.t. coeffs. */
+size_t eml_sh_work_floats(int H, int W, int lmax, int B);
+int eml_sh_analysis_f32(const float* pano, const float* rows, const float* weights, const float* fourier, const float* tab,
+                        int B, int H, int W, int lmax, float* coeffs, float* work, eml_stream_t stream);
+/* coeffs (B,K,3) -> rec (B,3,H,W) = weights[y] sum_k Y_k(x_p) coeffs[b,k,c] (`np.dot(SH_matrix, coeffs)` with shEvaluate,
+ * sphere_harmonics.py:60): per image row the Legendre sums to 2 lmax + 1 ring coefficients, then the Fourier sum along the
+ * row.  Also the gradient of eml_sh_analysis_f32 w.r.t. pano. */
+int eml_sh_synthesis_f32(const float* coeffs, const float* rows, const float* weights, const float* fourier, const float* tab,
+                         int B, int H, int W, int lmax, float* rec, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
