@@ -6,13 +6,15 @@ synthetic generator follows SURVEY 8d.
 ``ProjectorPanoramaBatcher`` makes the reference's per-sample dict from HDR panoramas on the device (``*.npy``, see
 ``RegressionNetwork.data.PanoramaDataset``): ``light_targets`` (``data.py:73-84``) and ``resize_bilinear`` (``data.py:70``)
 are the two operators of csrc/projector_prep.hip, the rest is ``PanoramaBatcher``'s crop / area resize / tonemap,
-``extract_mesh`` and the rasteriser."""
+``extract_mesh`` and the rasteriser.  ``resize_exr`` is the reference's panorama warp (``util.py:279-343``) on the device;
+``warp=`` / ``move_range=`` of the batcher apply it to the 128 x 256 panorama, so ``warped`` and ``map`` are those of the
+position the crop shows, as the reference's ``warpedHDROutputs`` files are (``data.py:73``)."""
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
 from ..RegressionNetwork.data import PanoramaBatcher, synthetic_batch
-from ..RegressionNetwork.util import convert_to_panorama, sphere_points, tonemap_raw
+from ..RegressionNetwork.util import PanoramaHandler, convert_to_panorama, sphere_points, tonemap_raw
 
 
 _ANCHORS = {}
@@ -107,6 +109,14 @@ def resize_bilinear(x, size, alpha=None, clip=False):
     return out
 
 
+def resize_exr(img, res_x=512, res_y=512, theta=0.0, phi=0.0, move=0.0):
+    """The reference's ``resize_exr(img, res_x, res_y)`` (``GenProjector/util.py:279-343``) on device tensors, one image
+    ``(H, W, 3)`` or a batch: ``res_x`` is the number of ROWS of the result and ``res_y`` its columns, as there; the three
+    constants of ``util.py:281`` are keywords (degrees, degrees, sphere radii; numbers or ``(B,)`` device tensors).  See
+    ``PanoramaHandler.warp_panorama``."""
+    return PanoramaHandler.warp_panorama(img, (int(res_y), int(res_x)), theta=theta, phi=phi, move=move)
+
+
 class ProjectorPanoramaBatcher(PanoramaBatcher):
     """Device panoramas ``(B, H, W, 3)`` -> the dict of the reference's ``LavalIndoorDataset.__getitem__``
     (``GenProjector/data.py:58-108``), the whole batch at once:
@@ -116,28 +126,33 @@ class ProjectorPanoramaBatcher(PanoramaBatcher):
     * ``crop`` ``(B, 3, 128, 128)``: ``TonemapHDR(2.4, 50, 0.5)`` of the perspective crop, resized (``data.py:69-70``) -- the
       resize takes the tonemap's ``P`` and ``alpha``, the full-size tonemapped crop is not made;
     * ``warped`` ``(B, 3, 128, 256)``, ``map`` ``(B, 1, 128, 256)``: ``light_targets(pano, alpha)`` (``data.py:73-84``);
-    * ``pano`` ``(B, 128, 256, 3)``: the rotated panorama area-resized, ``alpha`` ``(B,)``: the crop's tonemap alpha.
+    * ``pano`` ``(B, 128, 256, 3)``: the rotated panorama area-resized (and warped, if asked), ``alpha`` ``(B,)``: the crop's tonemap alpha.
 
     Views are drawn exactly as ``PanoramaBatcher`` draws them (same generator and seed, one azimuth per sample, the rotation
-    folded into the gathers), so ``warped`` is the panorama centred on the crop's viewing direction -- the reference reads a
-    panorama warped offline to the crop's position instead; that operator is not in the reference tree.
+    folded into the gathers), so ``warped`` is the panorama centred on the crop's viewing direction, seen from the camera's
+    own position.  The reference reads a panorama warped offline to the position the crop shows instead (``data.py:73``);
+    that operator is ``resize_exr`` (``GenProjector/util.py:279-343``): ``warp=`` / ``move_range=`` (see ``PanoramaBatcher``)
+    apply it to the 128 x 256 panorama before ``extract_mesh`` and ``light_targets``, the crop is untouched.
     ``regression=True`` adds ``PanoramaBatcher``'s ``distribution, intensity, rgb_ratio, ambient``; ``crop`` is then the
     full-size tonemapped crop the encoder reads and the 128 x 128 one goes under ``crop128`` (``JointTrainer`` uses it).
     The call only enqueues work."""
 
     CROP128 = (128, 128)
 
-    def __init__(self, anchors=128, crop_hw=(192, 256), fov_deg=60.0, device="cuda", seed=1234, regression=False, mesh=None):
-        super().__init__(anchors=anchors, crop_hw=crop_hw, fov_deg=fov_deg, device=device, seed=seed, mesh=mesh)
+    def __init__(self, anchors=128, crop_hw=(192, 256), fov_deg=60.0, device="cuda", seed=1234, regression=False, mesh=None,
+                 move_range=None):
+        super().__init__(anchors=anchors, crop_hw=crop_hw, fov_deg=fov_deg, device=device, seed=seed, mesh=mesh,
+                         move_range=move_range)
         self.regression = bool(regression)
 
-    def __call__(self, panos, deg=None, fov_deg=None):
+    def __call__(self, panos, deg=None, fov_deg=None, warp=None):
         deg, fov = self.view(panos, deg, fov_deg)
+        warp = self.warp_of(panos, warp)
         raw = tonemap_raw(self.crop(panos, deg, fov), self.tone.gamma, self.tone.percentile, self.tone.max_mapping, clip=True,
                           apply=self.regression)
         alpha = raw["alpha"].contiguous()
         crop128 = resize_bilinear(raw["P"], self.CROP128, alpha=alpha, clip=True)
-        small = self.small(panos, deg)
+        small = self.warped(self.small(panos, deg), warp)
         para, _ = self.mesh.compute(small)
         warped, mask = light_targets(small, alpha)
         out = {"input": gaussian_map(para["distribution"].float(), para["intensity"].float(), para["rgb_ratio"].float(),

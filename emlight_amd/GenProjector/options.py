@@ -15,6 +15,8 @@ default, so that ``train_laval.sh`` / ``test.sh`` run against this package uncha
 Options of this build that the reference does not have: ``--synthetic --iters_per_epoch --max_iters``, the VGG switches and
 ``--pano_dir DIR [--fov F]``: batches made on the GPU from a directory of ``*.npy`` HDR panoramas
 (``data.ProjectorPanoramaBatcher``); the dataset / display flags are ignored there as under ``--synthetic``.
+``--warp_move LO HI`` (train, with ``--pano_dir`` only): ``warped`` / ``map`` / ``input`` from the panorama warped to a drawn
+position along the view axis (``resize_exr``), as the reference's ``warpedHDROutputs`` files are.
 """
 import argparse
 import os
@@ -183,6 +185,8 @@ def train_parser():
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     add_train_options(ap)
     add_pano_options(ap)
+    from ..RegressionNetwork.data import add_warp_option
+    add_warp_option(ap)
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches (SURVEY 8d) instead of the Laval dataset")
     ap.add_argument("--iters_per_epoch", type=int, default=100, help="synthetic: iterations that make an epoch")
     ap.add_argument("--max_iters", type=int, default=0, help="stop after this many iterations (0: run niter + niter_decay epochs)")

@@ -28,6 +28,8 @@ def parse_args(argv=None):
     networks.add_vgg_arguments(ap)
     args = ap.parse_args(argv)
     options.resolve_gpu_ids(args.gpu_ids, options.world_from_env())
+    from ..RegressionNetwork.data import warp_move_range
+    args.move_range = warp_move_range(args)       # exits if --warp_move came without --pano_dir
     args.ignored_reference_flags = options.check_data_flags(args, ap, args.synthetic,
                                                             verbose=int(os.environ.get("RANK", "0")) == 0, pano_dir=args.pano_dir)
     return args
@@ -48,7 +50,8 @@ def make_pano_loader(args, device, rank, world):
     sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
     loader = DataLoader(ds, batch_size=args.batchSize, shuffle=sampler is None, sampler=sampler, drop_last=True, num_workers=2,
                         pin_memory=True)
-    return data.ProjectorPanoramaBatcher(fov_deg=args.fov, device=device, seed=1234 + rank), loader, sampler
+    return data.ProjectorPanoramaBatcher(fov_deg=args.fov, device=device, seed=1234 + rank,
+                                         move_range=getattr(args, "move_range", None)), loader, sampler
 
 
 def main(argv=None):

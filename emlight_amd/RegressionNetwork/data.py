@@ -102,6 +102,29 @@ class PanoramaDataset(Dataset):
                 "name": os.path.basename(path)[:-len(".npy")]}
 
 
+def add_warp_option(ap):
+    """``--warp_move LO HI`` of the three train mains (valid with ``--pano_dir`` only, see ``warp_move_range``)."""
+    ap.add_argument("--warp_move", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="--pano_dir: derive the targets from the panorama warped to a position `move` sphere radii along the "
+                         "view axis (negative: toward what the crop shows), one move per sample drawn uniformly in [LO, HI) "
+                         "(PanoramaBatcher(move_range=...)); default: the camera's own position")
+    return ap
+
+
+def warp_move_range(args):
+    """The parsed ``--warp_move`` as ``move_range`` (``None`` without the flag); exits with a message where the flag cannot
+    apply: without ``--pano_dir`` no panorama exists to warp."""
+    if getattr(args, "warp_move", None) is None:
+        return None
+    if not getattr(args, "pano_dir", None):
+        raise SystemExit("--warp_move applies to the batches made from --pano_dir panoramas; without --pano_dir there is no "
+                         "panorama to warp")
+    lo, hi = args.warp_move
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise SystemExit("--warp_move LO HI: finite values with LO <= HI, got %r %r" % (lo, hi))
+    return (float(lo), float(hi))
+
+
 class PanoramaBatcher:
     """Device panoramas ``(B, H, W, 3)`` -> the training dict of the reference's ``ParameterDataset`` (``data.py:46-84``):
 
@@ -113,11 +136,17 @@ class PanoramaBatcher:
 
     ``deg=None`` draws one azimuth in [0, 360) per sample from a seeded generator that lives on the device; a Python
     number holds for the batch, a ``(B,)`` device tensor gives one per sample (likewise ``fov_deg``).  The call only
-    enqueues work: no ``.item()``, no ``.cpu()``, no pageable copy.  ``mesh``: an ``extract_mesh`` (h=128, w=256) to share."""
+    enqueues work: no ``.item()``, no ``.cpu()``, no pageable copy.  ``mesh``: an ``extract_mesh`` (h=128, w=256) to share.
+
+    ``warp=(theta, phi, move)`` (numbers, or a ``(B, 3)`` device tensor) warps the 128 x 256 panorama to another position
+    before the targets are derived (``PanoramaHandler.warp_panorama``, the reference's ``resize_exr``); the crop is
+    untouched.  ``move_range=(lo, hi)`` at construction draws one ``move`` per sample uniformly in [lo, hi) from the same
+    generator, after the azimuth, with ``theta = phi = 0``; a ``warp=`` passed to the call wins.  With neither, the calls made
+    and every output are what they were without the arguments."""
 
     PANO_HW = (128, 256)
 
-    def __init__(self, anchors=96, crop_hw=(192, 256), fov_deg=60.0, device="cuda", seed=1234, mesh=None):
+    def __init__(self, anchors=96, crop_hw=(192, 256), fov_deg=60.0, device="cuda", seed=1234, mesh=None, move_range=None):
         from fractions import Fraction
         from .representation import extract_mesh
         from .util import TonemapHDR
@@ -130,12 +159,46 @@ class PanoramaBatcher:
         self.mesh = mesh if mesh is not None else extract_mesh(h=self.PANO_HW[0], w=self.PANO_HW[1], ln=anchors, device=device)
         self.tone = TonemapHDR(gamma=2.4, percentile=50, max_mapping=0.5)
         self.generator = None   # made on the device at the first random draw
+        if move_range is not None:
+            if len(move_range) != 2 or not (np.isfinite(move_range[0]) and np.isfinite(move_range[1]) and move_range[0] <= move_range[1]):
+                raise ValueError("move_range must be (lo, hi), finite, lo <= hi; got %r" % (move_range,))
+            move_range = (float(move_range[0]), float(move_range[1]))
+        self.move_range = move_range
 
-    def random_deg(self, B):
+    def _rand(self, B):
         if self.generator is None:
             self.generator = torch.Generator(device=self.device)
             self.generator.manual_seed(self.seed)
-        return torch.rand(B, generator=self.generator, device=self.device, dtype=torch.float64) * 360.0
+        return torch.rand(B, generator=self.generator, device=self.device, dtype=torch.float64)
+
+    def random_deg(self, B):
+        return self._rand(B) * 360.0
+
+    def random_move(self, B):
+        """One ``move`` per sample, uniform in ``move_range``, from the batcher's generator."""
+        lo, hi = self.move_range
+        return lo + self._rand(B) * (hi - lo)
+
+    def warp_of(self, panos, warp=None):
+        """The batch's warp as ``warp_panorama`` takes it: ``None`` (no warp) or ``(theta, phi, move)``, each a number or a
+        ``(B,)`` device tensor.  Call it after ``view``: a drawn ``move`` comes after the azimuth in the generator's sequence."""
+        B = panos.shape[0]
+        if warp is None:
+            return None if self.move_range is None else (0.0, 0.0, self.random_move(B))
+        if isinstance(warp, torch.Tensor):
+            if warp.shape != (B, 3):
+                raise ValueError("warp: expected (theta, phi, move) per sample, shape (%d, 3), got %s" % (B, tuple(warp.shape)))
+            return warp.unbind(1)
+        if len(warp) != 3:
+            raise ValueError("warp: expected (theta, phi, move), got %r" % (warp,))
+        return tuple(float(v) for v in warp)
+
+    def warped(self, small, warp):
+        """``small`` warped to the position ``warp`` stands for; ``small`` itself without one."""
+        if warp is None:
+            return small
+        from .util import PanoramaHandler
+        return PanoramaHandler.warp_panorama(small, None, theta=warp[0], phi=warp[1], move=warp[2])
 
     def view(self, panos, deg=None, fov_deg=None):
         """The batch's ``(deg, fov_deg)``: what was passed, else one drawn azimuth per sample and the constructor's field of
@@ -164,8 +227,9 @@ class PanoramaBatcher:
                 "rgb_ratio": para["rgb_ratio"].float(),
                 "ambient": para["ambient"].float() * alpha[:, None] / (128 * 256)}
 
-    def __call__(self, panos, deg=None, fov_deg=None):
+    def __call__(self, panos, deg=None, fov_deg=None, warp=None):
         deg, fov = self.view(panos, deg, fov_deg)
+        warp = self.warp_of(panos, warp)
         crop, alpha = self.tone(self.crop(panos, deg, fov))
-        para, _ = self.mesh.compute(self.small(panos, deg))
+        para, _ = self.mesh.compute(self.warped(self.small(panos, deg), warp))
         return {"crop": crop, **self.targets(para, alpha), "alpha": alpha}

@@ -4,7 +4,7 @@ torchrun-aware, same optimiser, loss weights, print/visualise/checkpoint cadence
 
     python -m emlight_amd.RegressionNetwork.train --synthetic --epochs 1
     torchrun --nproc-per-node 8 -m emlight_amd.RegressionNetwork.train --synthetic
-    python -m emlight_amd.RegressionNetwork.train --pano_dir DIR --fov 60      # crops and targets made on the GPU per step
+    python -m emlight_amd.RegressionNetwork.train --pano_dir DIR --fov 60 [--warp_move -0.6 0]      # crops and targets made on the GPU per step
 """
 import argparse
 import os
@@ -62,20 +62,24 @@ def build_parser():
                     help="directory of *.npy HDR panoramas (H, W, 3): every step crops a fresh random view of each panorama, "
                          "tonemaps it and derives the targets on the GPU (data.PanoramaBatcher); overrides --train_dir")
     ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
+    data.add_warp_option(ap)
     return ap
 
 
 def make_batcher(args, device):
     """The ``--pano_dir`` path's panorama -> training-batch step; ``None`` on the default paths (which stay as they are)."""
+    move_range = data.warp_move_range(args)   # exits if --warp_move came without --pano_dir
     if not args.pano_dir:
         return None
-    return data.PanoramaBatcher(anchors=args.anchors, crop_hw=tuple(args.crop_hw), fov_deg=args.fov, device=device)
+    return data.PanoramaBatcher(anchors=args.anchors, crop_hw=tuple(args.crop_hw), fov_deg=args.fov, device=device,
+                                move_range=move_range)
 
 
 def main(argv=None):
     from emlight_amd import _runtime
     _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
     args = build_parser().parse_args(argv)
+    data.warp_move_range(args)        # before any process group exists: a flag that cannot apply exits at once
 
     rank, local, world = init_distributed()
     device = "cuda:%d" % local

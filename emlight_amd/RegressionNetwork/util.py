@@ -3,7 +3,8 @@
 ``convert_to_panorama`` (reference ``util.py:222-245``) runs as one HIP kernel each way;
 ``sphere_points`` (``util.py:286-299``) is the small host helper the kept entry points need.
 ``PanoramaHandler`` (``util.py:69-185``: crop, rotate, resize) and ``TonemapHDR`` (``util.py:36-66``) run on device
-tensors, batched (csrc/pano_prep.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
+tensors, batched (csrc/pano_prep.hip); ``PanoramaHandler.warp_panorama`` is the panorama warp of ``GenProjector/util.py:279-343``
+(csrc/pano_warp.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
 EXR/vtk/cv2 I/O is out of scope.
 """
 import functools
@@ -257,6 +258,51 @@ class PanoramaHandler(object):
         _lib.check(_lib.lib().eml_pano_resize_area_f32(_lib.ptr(x), B, H, W, h, w, dg, _lib.ptr(deg_t), _lib.ptr(out),
                                                        _lib.current_stream()), "eml_pano_resize_area_f32")
         return out[0] if single else out
+
+    @staticmethod
+    def warp_panorama(hdr_img, new_shape=None, theta=0.0, phi=0.0, move=0.0, return_coords=False):
+        """The reference's ``resize_exr`` (``GenProjector/util.py:279-343``) with its three constants as arguments
+        (``eml_pano_warp_f32``): the panorama as seen after rotating the frame by ``theta`` (about x) and ``phi`` (about the
+        rotated y axis), both in degrees, and stepping ``move`` sphere radii along the rotated -z axis -- the crop looks
+        along +z, so a negative ``move`` steps toward what the crop shows.  ``(B, H, W, 3)`` float32 -> ``(B, h, w, 3)``,
+        bilinear with wrap-around on both axes; ``new_shape`` is ``(w, h)`` or an int ``h`` meaning ``(2h, h)`` as for
+        ``resize_panorama``, ``None`` keeps the source's size.  Each parameter: a Python number for the whole batch or a
+        ``(B,)`` device tensor; if any is a tensor the three are packed into a ``(B, 3)`` float64 device array (no host
+        synchronisation) and every sample is evaluated on its own.  By-value parameters that are not finite raise
+        ``ValueError``; a per-sample value that gives no finite position (NaN; ``|move| == 1`` at the one direction that
+        falls on the new viewpoint) gives NaN pixels.  ``return_coords``: also the float64 source positions ``(row, col)``,
+        ``(n, h, w, 2)`` with ``n = B`` for per-sample parameters, else 1 (``(h, w, 2)`` for a single image)."""
+        x, single = PanoramaHandler._batched(hdr_img, "hdr_img")
+        B, H, W, _ = x.shape
+        if new_shape is None:
+            w, h = W, H
+        elif isinstance(new_shape, tuple) and len(new_shape) == 2:
+            w, h = int(new_shape[0]), int(new_shape[1])
+        elif isinstance(new_shape, int):
+            w, h = 2 * new_shape, new_shape
+        else:
+            raise ValueError("new_shape must be (w, h), an int h or None, got %r" % (new_shape,))
+        if h < 1 or w < 1 or H < 1 or W < 1:
+            raise ValueError("warp_panorama: empty image, %d x %d -> %d x %d" % (H, W, h, w))
+        vals = [_per_sample(v, B, n) for v, n in ((theta, "theta"), (phi, "phi"), (move, "move"))]
+        params = None
+        if any(t is not None for _, t in vals):
+            params = torch.stack([t if t is not None else torch.full((B,), v, dtype=torch.float64, device=x.device)
+                                  for v, t in vals], dim=1).contiguous()
+            vals = [(0.0, None)] * 3
+        elif not all(np.isfinite(v) for v, _ in vals):
+            raise ValueError("warp_panorama: theta, phi and move must be finite, got %r" % ([v for v, _ in vals],))
+        n_sets = B if params is not None else 1
+        out = torch.empty(B, h, w, 3, dtype=torch.float32, device=x.device)
+        coords = torch.empty(n_sets, h, w, 2, dtype=torch.float64, device=x.device) if return_coords else None
+        if B > 0:       # an empty batch has no storage to point at
+            _lib.check(_lib.lib().eml_pano_warp_f32(_lib.ptr(x), B, H, W, h, w, vals[0][0], vals[1][0], vals[2][0],
+                                                    _lib.ptr(params), _lib.ptr(out), _lib.ptr(coords), _lib.current_stream()),
+                       "eml_pano_warp_f32")
+        if single:
+            out = out[0]
+            coords = coords[0] if return_coords else None
+        return (out, coords) if return_coords else out
 
 
 def tonemap_raw(img, gamma=2.4, percentile=50, max_mapping=0.5, clip=True, alpha=None, use_gamma=True, apply=True):

@@ -1,4 +1,4 @@
-"""ctypes binding of libemlight_hip.so (the C ABI declared in include/emlight_hip.h).
+"""ctypes binding of libemlight_hip.so (the C ABI declared in include/emlight_hip.h and include/emlight_hip_ext.h).
 
 The product path has NO fallback: if the shared library is missing or a symbol is absent,
 ``lib()`` raises -- a GPU box must run the HIP kernels or fail loudly.
@@ -236,6 +236,13 @@ SIGNATURES = {
     "eml_dense_head_pool_bwd_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, _int, _f32p, _int, _stream]),
 }
 
+# entry points added after the 131 above: declared in include/emlight_hip_ext.h, same library, same ABI version
+EXT_SIGNATURES = {
+    # panorama warp (resize_exr): rotate, translate, resample with wrap-around
+    "eml_pano_warp_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p,
+                                 _f32p, _f64p, _stream]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -258,7 +265,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C emlight_amd/csrc`. "
                 "There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

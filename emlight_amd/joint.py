@@ -21,7 +21,7 @@ all-reduce over RCCL/xGMI) and SPADE's batch norm synchronises its statistics (`
 
     python -m emlight_amd.joint --batch 8 --max_iters 10
     torchrun --nproc-per-node 8 -m emlight_amd.joint --batch 32
-    python -m emlight_amd.joint --pano_dir DIR --fov 60 --batch 8      # crops, targets, warped and map made on the GPU per step
+    python -m emlight_amd.joint --pano_dir DIR --fov 60 --batch 8 [--warp_move -0.6 0]      # crops, targets, warped and map made on the GPU per step
 """
 import argparse
 
@@ -31,6 +31,7 @@ import torch.nn.functional as F
 from .GenProjector import data as projector_data
 from .GenProjector import networks
 from .GenProjector.model_trainer import Trainer
+from .RegressionNetwork.data import add_warp_option, warp_move_range
 from .RegressionNetwork.engine import RegressionTrainer, init_distributed, regression_loss
 
 
@@ -134,6 +135,7 @@ def build_parser():
                          "makes the regression targets and the projector's warped / map on the GPU "
                          "(GenProjector.data.ProjectorPanoramaBatcher(regression=True)); --max_iters counts its steps")
     ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
+    add_warp_option(ap)
     networks.add_vgg_arguments(ap)
     return ap
 
@@ -149,7 +151,8 @@ def pano_batches(args, device, rank, world):
         raise SystemExit("--pano_dir %s holds %d panoramas, fewer than one global batch (%d)" % (args.pano_dir, len(ds),
                                                                                                 args.batch * world))
     batcher = projector_data.ProjectorPanoramaBatcher(anchors=args.anchors, crop_hw=tuple(args.crop_hw), fov_deg=args.fov,
-                                                      device=device, seed=1234 + rank, regression=True)
+                                                      device=device, seed=1234 + rank, regression=True,
+                                                      move_range=warp_move_range(args))
     sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
     loader = DataLoader(ds, batch_size=args.batch, shuffle=sampler is None, sampler=sampler, drop_last=True, num_workers=2,
                         pin_memory=True)
@@ -166,6 +169,7 @@ def main(argv=None):
     from emlight_amd import _runtime
     _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
     args = build_parser().parse_args(argv)
+    warp_move_range(args)             # before any process group exists: a flag that cannot apply exits at once
     rank, local, world = init_distributed()
     dev = "cuda:%d" % local
     tr = JointTrainer(networks.default_options(ngf=args.ngf, ndf=args.ndf, **networks.vgg_options(args, verbose=rank == 0)),
