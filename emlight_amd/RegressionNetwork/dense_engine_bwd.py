@@ -18,39 +18,6 @@ def _r16(v):
     return (v + 15) // 16 * 16
 
 
-def _side_stream(dev, prio):
-    """A second HIP stream on `dev`.  torch's pool only hands out priorities <= 0; a LOW-priority stream (prio > 0: the
-    background weight gradients must not take CUs from the critical chain) is created through the HIP runtime torch
-    has already loaded and wrapped as an ExternalStream."""
-    if prio <= 0:
-        return torch.cuda.Stream(device=dev, priority=prio)
-    hip = ctypes.CDLL("libamdhip64.so")
-    h = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        rc = hip.hipStreamCreateWithPriority(ctypes.byref(h), ctypes.c_uint(1), ctypes.c_int(prio))  # 1 = non-blocking
-    if rc != 0:
-        raise RuntimeError("hipStreamCreateWithPriority failed (%d)" % rc)
-    return torch.cuda.ExternalStream(h.value, device=dev)
-
-
-def _masked_stream(dev, n_cu, keep):
-    """A HIP stream restricted to the CUs i of [0, n_cu) with keep(i) (hipExtStreamCreateWithCUMask): a kernel launched
-    on it only ever occupies that subset, so a persistent grid sized for the subset never waits for a CU that another
-    stream's kernel holds."""
-    hip = ctypes.CDLL("libamdhip64.so")
-    words = (n_cu + 31) // 32
-    mask = (ctypes.c_uint32 * words)()
-    for i in range(n_cu):
-        if keep(i):
-            mask[i // 32] |= 1 << (i % 32)
-    h = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(h), ctypes.c_uint32(words), mask)
-    if rc != 0:
-        raise RuntimeError("hipExtStreamCreateWithCUMask failed (%d)" % rc)
-    return torch.cuda.ExternalStream(h.value, device=dev)
-
-
 class _BwdBuffers:
     def gf12(self, r):
         if self.GF12[r] is None:
@@ -72,8 +39,8 @@ class _BwdBuffers:
         self._gf12_new = lambda: torch.empty(maxP, 12, **f32)
         self.N12 = torch.empty(maxP, 12, **f32)     # narrow pass: finished gradient of the lower layer's 12 channels
         # the two-layer data-gradient pass's top 24 channels (the next pair's output channels) as two compact tensors: their
-        # readers then fetch 48 bytes per pixel instead of one or two 128-byte lines of a wide G row (EML_DGRAD_TOP=0: A/B)
-        self.TOP = torch.empty(2 * maxP * 12, **f32) if knob_flag("EML_DGRAD_TOP", True) else None   # (2, P, 12) per block
+        # readers then fetch 48 bytes per pixel instead of one or two 128-byte lines of a wide G row
+        self.TOP = torch.empty(2 * maxP * 12, **f32)   # (2, P, 12) per block
         # scratch sized from the network (widest block Kp, widest transition Ko) and the largest grid, not for
         # EMLight's default only
         kp, ko, g = enc.kp_max, max(enc.ko_max, 48), enc.grid_max
@@ -98,16 +65,9 @@ class _BwdBuffers:
         # side stream of the conv3x3 weight gradients (nothing downstream waits for dW2): own partial buffers per slot
         self.side = None
         if enc.overlap_wgrad(dev):
-            # EML_CU_SPLIT=m: the side stream owns the CUs with i % m == m - 1, the main chain of the backward runs on a
-            # stream that owns the rest (experiment: partitioned instead of competing for the same CUs)
-            m = int(os.environ.get("EML_CU_SPLIT", 0))
-            self.main_masked = None
-            if m > 1:
-                n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-                self.side = _masked_stream(dev, n_cu, lambda i: i % m == m - 1)
-                self.main_masked = _masked_stream(dev, n_cu, lambda i: i % m != m - 1)
-            else:
-                self.side = _side_stream(dev, int(os.environ.get("EML_SIDE_PRIO", 0)))
+            # it competes with the main chain for the same CUs: partitioning the chip by CU mask cost 12-38 %, and a low or a
+            # high stream priority made no difference (profiles/r03_overlap_ab.txt)
+            self.side = torch.cuda.Stream(device=dev)
             self.partW3 = [torch.empty(g * 2 * 27 * 256, **f32) for _ in range(self.ring)]
             self.ev_ready = [torch.cuda.Event() for _ in range(self.ring)]
             self.ev_done = [None] * self.ring
@@ -119,18 +79,6 @@ def run_backward(enc, ws, x, gpooled, need_x=False, need_params=None):
     the data passes ride on them -- and write those nobody asked for into scratch, which takes no gradient-bucket slot."""
     if getattr(ws, "bwd", None) is None:
         ws.bwd = _BwdBuffers(enc, ws, x.device)
-    masked = getattr(ws.bwd, "main_masked", None)
-    if masked is None:
-        return _run_backward(enc, ws, x, gpooled, need_x, need_params)
-    cur = torch.cuda.current_stream(x.device)
-    masked.wait_stream(cur)
-    with torch.cuda.stream(masked):
-        out = _run_backward(enc, ws, x, gpooled, need_x, need_params)
-    cur.wait_stream(masked)
-    return out
-
-
-def _run_backward(enc, ws, x, gpooled, need_x, need_params):
     L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
     m = enc.model
     f = m.features
@@ -141,8 +89,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
     B, _, H, W = x.shape
     G = enc._grid(dev)
     G3 = enc._grid3(dev)   # conv3x3 kernels: one 512-thread workgroup per CU (see HipDenseEncoder._grid3)
-    # (EML_D3_SHORT=1: the data gradient's 256-thread / 4-row-tile A/B geometry wants two workgroups per CU, csrc/dense_bwd.hip)
-    G3d = enc._tuned("EML_GRID3_DGRAD", 2 * G3 if knob_flag("EML_D3_SHORT", False) else G3)
+    G3d = enc._tuned("EML_GRID3_DGRAD", G3)
     Gw = enc._tuned("EML_GRID_WGRAD1", G)   # per-family knobs for A/B runs (default: the common 2 x #CU)
     Gd = enc._tuned("EML_GRID_DGRAD", G)
     Gb = min(enc.grid_max, 4 * enc._cu)
@@ -239,7 +186,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
         Pn = B * (Hb // 2) * (Wb // 2)
         Gbuf = bw.G[bi]
         gl0 = sum(enc.block_layers[:bi])   # global index of the block's first dense layer (the dropout masks' counter)
-        top2 = bw.TOP[:2 * P * 12].view(2, P, 12) if bw.TOP is not None else None
+        top2 = bw.TOP[:2 * P * 12].view(2, P, 12)
         # ---- last_norm backward (affine folded into the transition kernels' dz operand)
         _lib.check(L.eml_dense_bn_bwd_stats_f32(p(dY), ld_dy, p(tr["T"]), Ko, None, 0, 0, cout, Pn, p(tr["tmean"]),
                                                 p(tr["tistd"]), p(part), Gb, st), "eml_dense_bn_bwd_stats_f32")
@@ -367,7 +314,7 @@ def _run_backward(enc, ws, x, gpooled, need_x, need_params):
                 Lmb = conv2_backward(lb, 1, n12=True)
                 # the next pair (lb - 1, lb - 2) owns columns [cin_b - 24, cin_b): masked passes only (the bits the forward
                 # kept), and only where the fused conv3x3 backward / the narrow epilogue are what reads them
-                to_top = (top2 is not None and lb >= 2 and blk["layers"][la]["mask"] is not None and bw.side is None
+                to_top = (lb >= 2 and blk["layers"][la]["mask"] is not None and bw.side is None
                           and cin_b >= 24 and cin_b % 4 == 0)   # (block 3 starts at channel 150: quads straddle)
                 dgrad([la, lb], [0, 1], 0, cin_b, top=to_top)  # both layers, X read once, G updated once
                 have_top = to_top

@@ -29,16 +29,10 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// component t of a float4 (t is a compile-time constant after unrolling).  MFMA loops run t OUTERMOST so
-// that consecutive MFMAs hit different accumulators: back-to-back MFMAs on one accumulator pay the
-// 40-cycle dependent latency instead of the 32-cycle issue interval (MI355X_MICROARCH.md).
-__device__ __forceinline__ float f4c(const float4& v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
-__device__ __forceinline__ double shfl_xor_d(double v, int m) { return __shfl_xor(v, m, 64); }
+using eml::f32x4;
+using eml::f4c;
+using eml::mfma16;
+using eml::shfl_xor_d;
 
 constexpr int kTH = 8, kTW = 32, kHH = kTH + 2, kHW = kTW + 2;
 
@@ -60,28 +54,23 @@ constexpr int kGPass = kHH / kGRows;                        // 5 passes of float
 // G may be the block gradient (ldg = ld, c0 = the layer's channel offset) or the compact (P,12) tensor that
 // conv1x1_bwd_narrow_kernel leaves for the lower layer of a pair (ldg = 12, c0 = 0); cx is the layer's channel
 // offset in X / sB / sC either way.
-// WIDE (round 4): the halo tile is staged as 340 pixels x 3 float4 = 1020 items, two per thread, instead of five float2
+// WIDE: the halo tile is staged as 340 pixels x 3 float4 = 1020 items, two per thread, instead of five float2
 // passes over (2 rows x 34 columns x 6 float2) -- 4 (FUSE: with x) 16-byte loads per thread and tile instead of 10 eight-
 // byte ones, and the compact GF leaves as float4.  Needs the channel offsets to be multiples of 4 (blocks 1 and 2 of
 // EMLight's encoder; block 3 starts at channel 150 and keeps the float2 path).
-// TH (round 4): output rows per tile = waves per workgroup.  8 (512 threads, one workgroup per CU) is round 1's geometry and
-// the one that runs.  4 (256 threads, TWO independent workgroups per CU, EML_D3_SHORT=1) was the experiment "with one
-// workgroup per CU the two waves of a SIMD share a phase, so nobody issues MFMAs while both sit in the epilogue": measured
-// 15.34 against 14.43 ms per step -- SLOWER.  The kernel moves 4.0 TB/s with 43 % of its bytes written (dzn, GF): it sits on
-// what this part delivers for that read / write mix (4.0-4.7 TB/s, profiles/r03_row_access_probe.txt), not on its phases.
+// 4-row tiles in two 256-thread workgroups per CU measured slower (profiles/r04_ab_conv3x3.txt): the kernel moves 4.0 TB/s with
+// 43 % of its bytes written (dzn, GF) and sits on what this part delivers for that read / write mix (4.0-4.7 TB/s,
+// profiles/r03_row_access_probe.txt), not on its phases.
 // DROP (with FUSE): the staged g is multiplied by the layer's dropout mask / (1 - p) (eml_dropout.h), recomputed from the
 // forward's key at the halo pixel: the data gradient, its statistics and the compact GF all see the masked g.
-template <bool FUSE, bool WIDE, int TH, bool DROP = false>
-__global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
+template <bool FUSE, bool WIDE, bool DROP = false>
+__global__ __launch_bounds__(kBD, 2) void conv3x3_bwd_data_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
     const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
     double* __restrict__ partials /*[grid][48][2]*/, const float* __restrict__ Xb, int ldx, int cx,
     const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF, eml::DropKey dk) {
-  constexpr int HH = TH + 2, NT = TH * 64;
-  constexpr int GR = TH == 8 ? 2 : 1;                       // halo rows staged per pass of the float2 path
-  constexpr int kNarrowPass = HH / GR;
-  __shared__ __attribute__((aligned(16))) float g_l[2][HH * kHW * kPSG];
-  __shared__ double red[TH * 48 * 2];
+  __shared__ __attribute__((aligned(16))) float g_l[2][kHH * kHW * kPSG];
+  __shared__ double red[kTH * 48 * 2];
   __shared__ __attribute__((aligned(16))) float coef_l[24];   // WIDE + FUSE: sB | sC of the layer's 12 channels
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, kk = lane >> 4;
@@ -98,7 +87,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
 #pragma unroll
       for (int n = 0; n < 3; ++n) bw[tap][s][n] = W2[((size_t)(4 * s + kk) * 48 + 16 * n + r) * 9 + tap];
 
-  const int tx_n = (W + kTW - 1) / kTW, ty_n = (H + TH - 1) / TH;
+  const int tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
   const int ntiles = B * ty_n * tx_n;
   double s1[3][4], s2[3][4];  // sum dzn, sum dzn*z  (xhat is applied to the f64 totals at the end)
 #pragma unroll
@@ -106,11 +95,11 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
 #pragma unroll
     for (int g = 0; g < 4; ++g) s1[n][g] = s2[n][g] = 0.0;
 
-  // staging map (narrow): GR halo rows x 34 columns x 6 float2 per pass (408 / 204 threads; the rest duplicate the last item)
-  // staging map (WIDE): item t = tid + NT * it (< HH * 34 * 3, the tail duplicates the last): halo pixel t / 3, float4 t % 3
-  constexpr int kWideItems = HH * kHW * 3;
-  constexpr int kPass = WIDE ? (kWideItems + NT - 1) / NT : kNarrowPass;
-  const int st = min(tid, GR * kHW * 6 - 1);
+  // staging map (narrow): kGRows halo rows x 34 columns x 6 float2 per pass (408 threads; the rest duplicate the last item)
+  // staging map (WIDE): item t = tid + kBD * it (< kHH * 34 * 3, the tail duplicates the last): halo pixel t / 3, float4 t % 3
+  constexpr int kWideItems = kHH * kHW * 3;
+  constexpr int kPass = WIDE ? (kWideItems + kBD - 1) / kBD : kGPass;
+  const int st = min(tid, kGRows * kHW * 6 - 1);
   const int s_row = st / (kHW * 6), s_rem = st - s_row * (kHW * 6);
   const int s_hx = s_rem / 6, s_q = s_rem - 6 * s_hx;
   const int s_dst = (s_row * kHW + s_hx) * kPSG + 2 * s_q;
@@ -122,7 +111,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
   if constexpr (WIDE) {
 #pragma unroll
     for (int it = 0; it < kWP; ++it) {
-      const int t = min(tid + NT * it, kWideItems - 1), hp = t / 3;
+      const int t = min(tid + kBD * it, kWideItems - 1), hp = t / 3;
       w_q[it] = t - 3 * hp;
       w_hy[it] = hp / kHW;
       w_hx[it] = hp - w_hy[it] * kHW;
@@ -145,18 +134,18 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     if constexpr (WIDE) {
 #pragma unroll
       for (int it = 0; it < kWP; ++it) {
-        const int gy = ty * TH - 1 + w_hy[it], gx = tx * kTW - 1 + w_hx[it];
+        const int gy = ty * kTH - 1 + w_hy[it], gx = tx * kTW - 1 + w_hx[it];
         w_ok[it] = gy >= 0 && gy < H && gx >= 0 && gx < W;
         w_pix[it] = (b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1);
         if constexpr (FUSE) {
           // a pixel of the tile itself (not halo); the duplicated tail items of pass 1 write the same value twice
-          w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= TH && w_hx[it] >= 1 && w_hx[it] <= kTW;
+          w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
         }
       }
       return;
     }
     const int gx = tx * kTW - 1 + s_hx;
-    s_y0 = ty * TH - 1 + s_row;
+    s_y0 = ty * kTH - 1 + s_row;
     s_col = gx >= 0 && gx < W;
     const size_t col = (size_t)b * H * W + min(max(gx, 0), W - 1);
     if constexpr (DROP) s_pix0 = (unsigned)col;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     if constexpr (FUSE) {
       s_srcx = Xb + col * ldx + cx + 2 * s_q;
       s_gf = GF + col * 12 + 2 * s_q;
-      s_own = s_col && tid < GR * kHW * 6 && s_hx >= 1 && s_hx <= kTW;  // a column of the tile itself (not halo)
+      s_own = s_col && tid < kGRows * kHW * 6 && s_hx >= 1 && s_hx <= kTW;  // a column of the tile itself (not halo)
     }
   };
   auto stage_load = [&](int it) {  // unconditional (clamped): exec-masked loads make the compiler stall MFMAs on them
@@ -173,7 +162,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
       if constexpr (FUSE) xt4[it] = *reinterpret_cast<const float4*>(Xb + (size_t)w_pix[it] * ldx + cx + 4 * w_q[it]);
       return;
     }
-    const size_t row = (size_t)min(max(s_y0 + GR * it, 0), H - 1) * W;
+    const size_t row = (size_t)min(max(s_y0 + kGRows * it, 0), H - 1) * W;
     gt[it] = *reinterpret_cast<const float2*>(s_src + row * ldg);
     if constexpr (FUSE) xt[it] = *reinterpret_cast<const float2*>(s_srcx + row * ldx);
   };
@@ -198,7 +187,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
       }
       return;
     }
-    const int gy = s_y0 + GR * it;
+    const int gy = s_y0 + kGRows * it;
     const bool ok = s_col && gy >= 0 && gy < H;
     float2 v;
     if constexpr (FUSE) {
@@ -213,10 +202,10 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
       v.x = ok ? gt[it].x : 0.f;
       v.y = ok ? gt[it].y : 0.f;
     }
-    *reinterpret_cast<float2*>(dst + s_dst + it * GR * kHW * kPSG) = v;
+    *reinterpret_cast<float2*>(dst + s_dst + it * kGRows * kHW * kPSG) = v;
     if constexpr (FUSE) {
-      const int hy = s_row + GR * it;  // halo row 0..HH-1; rows 1..TH are the tile's own
-      if (s_own && ok && hy >= 1 && hy <= TH) *reinterpret_cast<float2*>(s_gf + (size_t)gy * W * 12) = v;
+      const int hy = s_row + kGRows * it;  // halo row 0..kHH-1; rows 1..kTH are the tile's own
+      if (s_own && ok && hy >= 1 && hy <= kTH) *reinterpret_cast<float2*>(s_gf + (size_t)gy * W * 12) = v;
     }
   };
 
@@ -238,7 +227,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
     float* gn = g_l[cur ^ 1];
     const int b = tile / (ty_n * tx_n), rem = tile - b * (ty_n * tx_n);
     const int ty = rem / tx_n, tx = rem - ty * tx_n;
-    const int gy = ty * TH + wave;
+    const int gy = ty * kTH + wave;
     // this lane's two output pixels (row gy, columns 16m + r); clamped copies for the unconditional z loads
     size_t prow[2];
     bool pv[2];
@@ -343,7 +332,7 @@ __global__ __launch_bounds__(TH * 64, 2) void conv3x3_bwd_data_kernel(
   if (tid < 48) {
     double t1 = 0.0, t2 = 0.0;
 #pragma unroll
-    for (int w8 = 0; w8 < TH; ++w8) {
+    for (int w8 = 0; w8 < kTH; ++w8) {
       t1 += red[(w8 * 48 + tid) * 2 + 0];
       t2 += red[(w8 * 48 + tid) * 2 + 1];
     }
@@ -369,7 +358,7 @@ constexpr int kGL = kTH * kTW * 12;   // floats of a tile's own g pixels in LDS 
 // of the tile's 256 x 12 own pixels, staged by TWO 16-byte loads per thread, instead of 32 four-byte loads per lane and
 // tile -- 42 vector-memory instructions per wave and tile become 12.  (Round 4's gather-GEMM measurements priced a
 // vector-memory instruction at ~45 matrix-pipe cycles whatever it fetches: it holds the issuing wave ~60 cycles.)
-// GLDS = false keeps the round-1 register path for the A/B (EML_W3_GREG=1).
+// GLDS = false is the register path, for slices that are not 16-byte aligned.
 template <bool GLDS>
 __global__ __launch_bounds__(kBW) void conv3x3_bwd_weight_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ Z, const float* __restrict__ scale2,
@@ -484,20 +473,17 @@ __global__ __launch_bounds__(kBW) void conv3x3_bwd_weight_kernel(
 #pragma unroll
     for (int i = 0; i < 7; ++i) av[0][i] = tile_l[aoff[i]];
     if constexpr (GLDS) gvl[0] = gl_c[0];
-#ifndef EML_WX   // experiment builds (-DEML_WX=<bits>): 1 = no staging of the next tile (wrong results), 2 = no barrier,
-#define EML_WX 0  // 4 = no scheduling fences in the k-loop, 8 = reads interleaved with the MFMAs by a sched_group_barrier pipeline
-#endif
 #pragma unroll
     for (int ks = 0; ks < 32; ++ks) {
-      if (!(EML_WX & 1) && ks < kHH) stage_load(ks);
-      if (!(EML_WX & 1) && GLDS && ks >= kHH && ks < kHH + 2) gq_load(ks - kHH);
+      if (ks < kHH) stage_load(ks);
+      if (GLDS && ks >= kHH && ks < kHH + 2) gq_load(ks - kHH);
       if (ks + 1 < 32) {
         const float* base = tile_l + (((ks + 1) >> 3) * kHW + 4 * ((ks + 1) & 7)) * kPSW;
 #pragma unroll
         for (int i = 0; i < 7; ++i) av[(ks + 1) & 1][i] = base[aoff[i]];
         if constexpr (GLDS) gvl[(ks + 1) & 1] = gl_c[4 * (ks + 1) * 12];
       }
-      if (!(EML_WX & 12)) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       float gv;
       if constexpr (GLDS) {
         gv = r < 12 ? gvl[ks & 1] : 0.f;   // lanes 12..15 of a row: the unused MFMA columns
@@ -508,20 +494,12 @@ __global__ __launch_bounds__(kBW) void conv3x3_bwd_weight_kernel(
 #pragma unroll
       for (int i = 0; i < 7; ++i) acc[i] = mfma16(av[ks & 1][i], gv, acc[i]);
       if constexpr (!GLDS) g_load(ks);  // next tile's value, in place
-      if (!(EML_WX & 1) && GLDS && ks >= 32 - kHH - 2 && ks < 32 - kHH) gq_commit(ks - (32 - kHH - 2), gl_n);
-      if (!(EML_WX & 1) && ks >= 32 - kHH) stage_commit(ks - (32 - kHH), tile_n);
-      if (EML_WX & 8) {   // experiment: the next step's LDS reads one by one in the shadow of this step's MFMAs (no burst)
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      if (!(EML_WX & 4)) __builtin_amdgcn_sched_barrier(0);
+      if (GLDS && ks >= 32 - kHH - 2 && ks < 32 - kHH) gq_commit(ks - (32 - kHH - 2), gl_n);
+      if (ks >= 32 - kHH) stage_commit(ks - (32 - kHH), tile_n);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    if (!(EML_WX & 2)) eml::lds_barrier();
-    if (!(EML_WX & 1)) cur ^= 1;
+    eml::lds_barrier();
+    cur ^= 1;
   }
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
@@ -536,15 +514,12 @@ __global__ __launch_bounds__(kBW) void conv3x3_bwd_weight_kernel(
 
 
 // =============================================================================== conv3x3 backward: data + weight, one pass
-// Round 4: conv3x3_bwd_data is bound by HBM (4.0 TB/s, 43 % of it written) with the matrix pipe half
-// idle; conv3x3_bwd_weight is bound by the matrix pipe and then re-reads the g and z tiles the data gradient had just
-// staged (24.8 GB per step).  Here one 512-thread workgroup does both for a tile: the g halo tile (double-buffered) feeds
-// the data gradient (K = 9 x 12) and, through its own-pixel rows, the weight gradient's k = pixel operand; the BN2(z)
-// halo tile -- the weight gradient's other operand -- is read ONCE (10 x 34 pixels, +33 % over the tile's own z, which the
-// statistics still take from HBM/L2 as raw z) into a single LDS buffer, refilled for the next tile from registers between
-// two barriers.  The data gradient's 81 weight fragments live in LDS (they were 81 VGPRs); the weight gradient's
-// accumulators persist across tiles exactly as in conv3x3_bwd_weight_kernel (same deal of the 27 (tap, 16-channel) tiles
-// to waves and halves, same tile order per workgroup -> bitwise the same partials for the same grid).
+// conv3x3_bwd_data is bound by HBM (4.0 TB/s, 43 % of it written) with the matrix pipe half idle; conv3x3_bwd_weight is bound by
+// the matrix pipe and then re-reads the g and z tiles the data gradient had just staged (24.8 GB per step).  Here one 512-thread
+// workgroup does both for a tile, in two phases between LDS barriers: A, the data gradient (K = 9 x 12) from the double-buffered
+// g halo tile, its 81 weight fragments in LDS; B, the weight gradient, with the data gradient's epilogue (statistics, dzn stores)
+// riding on its MFMAs.  With one workgroup per CU the two waves of a SIMD share every phase, so nothing but MFMA-fed work sits
+// between the barriers.
 #ifdef EML_STAMPS   // experiment build (tools/exp_build.sh stamps -DEML_STAMPS): shader-clock cycles wave 0 of every workgroup spends
 // in each part of a tile, summed over tiles and workgroups: [0] phase A, [1] barrier 2, [2] phase B, [3] barrier 1, [4] tiles
 __device__ unsigned long long eml_c3_stamps[8];
@@ -557,327 +532,24 @@ __device__ unsigned long long eml_c3_stamps[8];
 #else
 #define EML_C3_STAMP(slot) do {} while (0)
 #endif
+// The weight gradient is TAP-PACKED.  With the 12 output channels as the MFMA columns (12 of 16 used) the 27 (tap, 16 input
+// channels) accumulator tiles of
+//     dW2[o][c][tap] = sum_p g[p][o] * zn[p + d_tap][c]
+// cost 224 MFMAs per wave and 256-pixel tile, on the BN2(z) HALO tile (10 x 34 pixels, each read 9 times).  Here the sum runs
+// over the pixel p' = p + d that zn is taken at:
+//     dW2[(tap, o)][c] = sum_{p'} g[p' - d_tap][o] * zn[p'][c]
+// rows (tap, o) = 108 of 112 in 7 row tiles, columns c = 48 in 3: 21 accumulator tiles instead of 27, 168 MFMAs per wave and tile
+// (profiles/r06_c3bwd_tp_stamps.txt).  The operand that needs neighbours is g, whose halo tile the data gradient stages anyway
+// (a per-lane offset into it per row tile: ds_read_b32); z is needed at the tile's own 256 pixels only and is staged RAW (no
+// halo): BN2's affine is one fma on the fragment, and the data gradient's BatchNorm statistics read the same raw rows from LDS
+// instead of a second time from L2.  The eight waves' accumulators are summed through LDS once, after the last tile (fixed
+// order): one partial row of 21 x 256 floats per workgroup.
 // Needs the fused BN1 affine (X given).  A16: the 12-channel slices of G and X are 16-byte aligned (blocks 1 and 2); otherwise
 // (block 3 of EMLight's encoder starts at channel 150) each staged item is fetched as two 8-byte loads.
 // DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
 // STORE_GF: also leave the compact GF (P, 12) of the staged g -- only a SEPARATE conv3x3_bwd_weight launch reads it, so the
-// launcher instantiates <.., false> when the caller passes GF == NULL (the default path: this kernel forms dW2 itself).
-template <bool A16, bool DROP = false, bool STORE_GF = true>
-__global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_kernel(
-    const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
-    const float* __restrict__ zmean, const float* __restrict__ zistd, float* __restrict__ DZ, int B, int H, int W,
-    double* __restrict__ partials /*[grid][48][2]*/, const float* __restrict__ Xb, int ldx, int cx,
-    const float* __restrict__ sB, const float* __restrict__ sC, float* __restrict__ GF,
-    const float* __restrict__ scale2, const float* __restrict__ shift2, float* __restrict__ partialW /*[2*grid][27][16][16]*/,
-    eml::DropKey dk) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int kGT = kHH * kHW * kPSG;                 // floats of a g halo tile
-  float* g_l = smem;                                    // [2][kGT]
-  float* z_l = g_l + 2 * kGT;                           // [kHH * kHW][kPSW]   BN2(z) halo tile, zero outside the image
-  float* w_l = z_l + kHH * kHW * kPSW;                  // [27][3][64]         data-gradient A fragments
-  float* coef_l = w_l + 27 * 3 * 64;                    // [24 (+8)]           sB | sC of the layer's 12 channels
-  double* red = reinterpret_cast<double*>(coef_l + 32); // [8][48][2]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, kk = lane >> 4;
-  const int half = wave >> 2, w4 = wave & 3;
-
-  // data-gradient fragments (D^T form): entry ((tap*3 + s)*3 + n)*64 + (kk*16 + r) = W2[o = 4s + kk][c = 16n + r][tap]
-  for (int e = tid; e < 27 * 3 * 64; e += 512) {
-    const int l = e & 63, g3 = e >> 6, n = g3 % 3, ts = g3 / 3, s3 = ts % 3, tap = ts / 3;
-    w_l[e] = W2[((size_t)(4 * s3 + (l >> 4)) * 48 + 16 * n + (l & 15)) * 9 + tap];
-  }
-  if (tid < 24) coef_l[tid] = tid < 12 ? sB[cx + tid] : sC[cx + tid - 12];
-
-  // weight-gradient accumulators and operand offsets (conv3x3_bwd_weight_kernel)
-  f32x4 accw[7];
-  int aoff[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    accw[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int idx = min(w4 + 4 * i, 26), tap = idx / 3, mc = idx - 3 * tap;
-    aoff[i] = ((tap / 3 + 4 * half) * kHW + (tap % 3) + kk) * kPSW + 16 * mc + r;
-  }
-  const int tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
-  const int ntiles = B * ty_n * tx_n;
-  // BatchNorm statistics: f64 running sums per (wave, channel) in LDS (`red`), updated once per tile by the lane that owns
-  // the channel after a DPP reduction over the 16 pixel lanes -- as 48 VGPRs of doubles they pushed the kernel into spills
-  for (int e = tid; e < 8 * 48 * 2; e += 512) red[e] = 0.0;
-
-  // ---- g halo staging (the WIDE map of conv3x3_bwd_data_kernel): item t = tid + 512*it, halo pixel t / 3, float4 t % 3
-  constexpr int kWideItems = kHH * kHW * 3;
-  int w_hy[2], w_hx[2], w_q[2], w_pix[2];
-  bool w_ok[2], w_own[2];
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int t = min(tid + 512 * it, kWideItems - 1), hp = t / 3;
-    w_q[it] = t - 3 * hp;
-    w_hy[it] = hp / kHW;
-    w_hx[it] = hp - w_hy[it] * kHW;
-  }
-  float4 gt4[2], xt4[2];
-  // ---- z halo staging (conv3x3_bwd_weight_kernel): thread = (halo column, 16-byte slice), one halo row per pass
-  const int s_hx = min(tid / 12, kHW - 1), s_q = tid % 12;
-  const float4 sc = *reinterpret_cast<const float4*>(scale2 + 4 * s_q);
-  const float4 sh = *reinterpret_cast<const float4*>(shift2 + 4 * s_q);
-  const int s_dst = s_hx * kPSW + 4 * s_q;
-  float4 zt[kHH];
-  const float* s_src = Z;
-  int s_y0 = 0;
-  bool s_col = false;
-  auto stage_begin = [&](int tile) {
-    const int b = tile / (ty_n * tx_n), rem = tile - b * (ty_n * tx_n);
-    const int ty = rem / tx_n, tx = rem - ty * tx_n;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int gy = ty * kTH - 1 + w_hy[it], gx = tx * kTW - 1 + w_hx[it];
-      w_ok[it] = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      w_pix[it] = (b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1);
-      if constexpr (STORE_GF) w_own[it] = w_ok[it] && w_hy[it] >= 1 && w_hy[it] <= kTH && w_hx[it] >= 1 && w_hx[it] <= kTW;
-    }
-    const int gx = tx * kTW - 1 + s_hx;
-    s_y0 = ty * kTH - 1;
-    s_col = gx >= 0 && gx < W;
-    s_src = Z + ((size_t)b * H * W + min(max(gx, 0), W - 1)) * 48 + 4 * s_q;
-  };
-  auto g_load = [&](int it) {   // unconditional, clamped
-    const float* gp = G + (size_t)w_pix[it] * ldg + c0 + 4 * w_q[it];
-    const float* xp = Xb + (size_t)w_pix[it] * ldx + cx + 4 * w_q[it];
-    if constexpr (A16) {
-      gt4[it] = *reinterpret_cast<const float4*>(gp);
-      xt4[it] = *reinterpret_cast<const float4*>(xp);
-    } else {
-      const float2 g0 = *reinterpret_cast<const float2*>(gp), g1 = *reinterpret_cast<const float2*>(gp + 2);
-      const float2 x0 = *reinterpret_cast<const float2*>(xp), x1 = *reinterpret_cast<const float2*>(xp + 2);
-      gt4[it] = make_float4(g0.x, g0.y, g1.x, g1.y);
-      xt4[it] = make_float4(x0.x, x0.y, x1.x, x1.y);
-    }
-  };
-  auto g_commit = [&](int it, float* dst) {
-    const float4 fb4 = *reinterpret_cast<const float4*>(coef_l + 4 * w_q[it]);
-    const float4 fc4 = *reinterpret_cast<const float4*>(coef_l + 12 + 4 * w_q[it]);
-    float4 v;
-    v.x = fmaf(fb4.x, xt4[it].x, gt4[it].x) + fc4.x;
-    v.y = fmaf(fb4.y, xt4[it].y, gt4[it].y) + fc4.y;
-    v.z = fmaf(fb4.z, xt4[it].z, gt4[it].z) + fc4.z;
-    v.w = fmaf(fb4.w, xt4[it].w, gt4[it].w) + fc4.w;
-    if constexpr (DROP) v = eml::drop4(dk, (unsigned)w_pix[it], (unsigned)w_q[it], v);
-    if (!w_ok[it]) v = make_float4(0.f, 0.f, 0.f, 0.f);
-    float* d = dst + (w_hy[it] * kHW + w_hx[it]) * kPSG + 4 * w_q[it];   // 56-byte pixel stride: 8-byte aligned
-    *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
-    *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
-    if constexpr (STORE_GF)
-      if (w_own[it]) *reinterpret_cast<float4*>(GF + (size_t)w_pix[it] * 12 + 4 * w_q[it]) = v;
-  };
-  auto z_load = [&](int it) {
-    zt[it] = *reinterpret_cast<const float4*>(s_src + (size_t)min(max(s_y0 + it, 0), H - 1) * W * 48);
-  };
-  auto z_commit = [&](int it, int y0, bool col) {
-    const bool ok = col && y0 + it >= 0 && y0 + it < H;
-    float4 v;
-    v.x = ok ? fmaf(zt[it].x, sc.x, sh.x) : 0.f;
-    v.y = ok ? fmaf(zt[it].y, sc.y, sh.y) : 0.f;
-    v.z = ok ? fmaf(zt[it].z, sc.z, sh.z) : 0.f;
-    v.w = ok ? fmaf(zt[it].w, sc.w, sh.w) : 0.f;
-    *reinterpret_cast<float4*>(z_l + s_dst + it * kHW * kPSW) = v;   // threads >= 408 duplicate column 33
-  };
-
-  int tile = blockIdx.x, cur = 0;
-  __syncthreads();   // coef_l, w_l, red
-  if (tile < ntiles) {
-    stage_begin(tile);
-    g_load(0);
-    g_load(1);
-#pragma unroll
-    for (int it = 0; it < kHH; ++it) z_load(it);   // committed by the first phase A, like every later tile's
-    g_commit(0, g_l);
-    g_commit(1, g_l);
-  }
-  __syncthreads();
-  // Per tile: phase A (data gradient) with the z halo's LDS commit riding on it; barrier; phase B (weight gradient) with
-  // the data gradient's epilogue (statistics, dzn stores) and the next tile's z halo loads riding on it; barrier.  Nothing
-  // but MFMA-fed work sits between the barriers: with one workgroup per CU the two waves of a SIMD share every phase, so
-  // any serial section (the epilogue was ~150 VALU + 6 stores per lane, the z commit 10 ds_write_b128) idled the matrix pipe.
-#ifdef EML_STAMPS
-  unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last = __builtin_readcyclecounter();
-#endif
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int nxt = tile + gridDim.x;
-    const float* gc = g_l + cur * kGT;
-    float* gn = g_l + (cur ^ 1) * kGT;
-    const int b = tile / (ty_n * tx_n), rem = tile - b * (ty_n * tx_n);
-    const int ty = rem / tx_n, tx = rem - ty * tx_n;
-    const int gy = ty * kTH + wave;
-    size_t prow[2];
-    bool pv[2];
-    float4 zr[2][3];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int gx = tx * kTW + 16 * m + r;
-      pv[m] = gy < H && gx < W;
-      prow[m] = ((size_t)(b * H + min(gy, H - 1)) * W + min(gx, W - 1)) * 48;
-    }
-    // validity of THIS tile's z halo rows / column (stage_begin below moves on to the next tile)
-    const int cz_y0 = s_y0;
-    const bool cz_col = s_col;
-    stage_begin(nxt < ntiles ? nxt : tile);   // (the last tile re-stages itself: loads stay unconditional)
-
-    // ------------------------------------------------------------------ phase A: data gradient (162 MFMAs per wave)
-    f32x4 acc[2][3];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float aq[2][2], wq[2][3];
-#pragma unroll
-    for (int n = 0; n < 3; ++n) wq[0][n] = w_l[n * 64 + lane];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) aq[0][m] = gc[((wave + 2) * kHW + 16 * m + r + 2) * kPSG + kk];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-      for (int s3 = 0; s3 < 3; ++s3) {
-        const int gi = tap * 3 + s3;
-        if (gi < 2) {
-          g_load(gi);
-          __builtin_amdgcn_sched_barrier(0);
-        } else if (gi < 2 + kHH) {
-          z_commit(gi - 2, cz_y0, cz_col);   // this tile's BN2(z) halo row: nobody reads z_l before the barrier below
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        // operands of group gi + 1 are requested before the MFMAs of group gi (read right in front of their MFMAs every
-        // group of 6 waited out an LDS round trip)
-        if (gi + 1 < 27) {
-          const int tn = (gi + 1) / 3, sn = (gi + 1) - 3 * tn, dyn = tn / 3, dxn = tn - 3 * dyn;
-#pragma unroll
-          for (int n = 0; n < 3; ++n) wq[(gi + 1) & 1][n] = w_l[((gi + 1) * 3 + n) * 64 + lane];
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-            aq[(gi + 1) & 1][m] = gc[((wave + 2 - dyn) * kHW + 16 * m + r + 2 - dxn) * kPSG + 4 * sn + kk];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 3; ++n) acc[m][n] = mfma16(wq[gi & 1][n], aq[gi & 1][m], acc[m][n]);  // D[channel][pixel]
-        if (gi >= 25) {
-          __builtin_amdgcn_sched_barrier(0);
-          g_commit(gi - 25, gn);
-        }
-      }
-    }
-    EML_C3_STAMP(0);
-    eml::lds_barrier();          // this tile's z halo is in place (and g_l[cur ^ 1] complete)
-    EML_C3_STAMP(1);
-    // ------------------------------------------------------------------ phase B: weight gradient (216 MFMAs per wave)
-    // k = pixel: lane (kk, o = r) takes g of own pixel 128*half + 4*ks + kk from the g halo tile (halo row / column + 1);
-    // the next tile's z halo rows are requested under the first 10 k-steps and committed after the barrier below
-    const float* gl_c = gc + ((4 * half + 1) * kHW + kk + 1) * kPSG + min(r, 11);
-    float av[2][7], gvl[2];   // both operands are read one k-step ahead of their MFMAs
-#pragma unroll
-    for (int i = 0; i < 7; ++i) av[0][i] = z_l[aoff[i]];
-    gvl[0] = gl_c[0];
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) {
-      // requests riding on this phase: the tile's own raw z rows (statistics, k-steps 0..5), then the NEXT tile's z halo
-      if (ks < 6) zr[ks / 3][ks % 3] = *reinterpret_cast<const float4*>(Z + prow[ks / 3] + 16 * (ks % 3) + 4 * kk);
-      else if (ks < 6 + kHH) z_load(ks - 6);
-      if (ks + 1 < 32) {
-        const float* base = z_l + (((ks + 1) >> 3) * kHW + 4 * ((ks + 1) & 7)) * kPSW;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) av[(ks + 1) & 1][i] = base[aoff[i]];
-        gvl[(ks + 1) & 1] = gl_c[(((ks + 1) >> 3) * kHW + 4 * ((ks + 1) & 7)) * kPSG];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const float gv = r < 12 ? gvl[ks & 1] : 0.f;   // (zero outside the image: staged so)
-#pragma unroll
-      for (int i = 0; i < 7; ++i) accw[i] = mfma16(av[ks & 1][i], gv, accw[i]);
-      // the data gradient's epilogue, piecewise behind these MFMAs: statistics of channel group n at k-step 16 + n (its z
-      // rows were requested ten k-steps ago), then one 16-byte dzn store per k-step
-      if (ks >= 6 + kHH && ks < 9 + kHH) {
-        const int n = ks - (6 + kHH);
-        float l1[4] = {0.f, 0.f, 0.f, 0.f}, l2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const float4 z = zr[m][n];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const float v = pv[m] ? acc[m][n][g] : 0.f;
-            l1[g] += v;
-            l2[g] = fmaf(v, f4c(z, g), l2[g]);
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float t1 = eml::row16_sum(l1[g]), t2 = eml::row16_sum(l2[g]);   // over this tile row's 32 pixels
-          if (r == 0) {   // wave-private slots: no other lane touches them
-            double* d = red + (wave * 48 + 16 * n + 4 * kk + g) * 2;
-            d[0] += (double)t1;
-            d[1] += (double)t2;
-          }
-        }
-      } else if (ks >= 9 + kHH && ks < 15 + kHH) {
-        const int si = ks - (9 + kHH), m = si / 3, n = si - 3 * m;
-        if (pv[m])
-          *reinterpret_cast<float4*>(DZ + prow[m] + 16 * n + 4 * kk) =
-              make_float4(acc[m][n][0], acc[m][n][1], acc[m][n][2], acc[m][n][3]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    EML_C3_STAMP(2);
-    eml::lds_barrier();          // everyone is done with z_l and g_l[cur]
-    EML_C3_STAMP(3);
-#ifdef EML_STAMPS
-    st_acc[4] += 1;
-#endif
-    cur ^= 1;
-  }
-#ifdef EML_STAMPS
-  if (tid == 0)
-    for (int i = 0; i < 5; ++i) atomicAdd(&eml_c3_stamps[i], st_acc[i]);
-#endif
-  // ---- outputs: weight-gradient partials per (workgroup, half), then the BatchNorm statistics
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int idx = w4 + 4 * i;
-    if (idx < 27) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        partialW[((((size_t)blockIdx.x * 2 + half) * 27 + idx) * 16 + 4 * kk + g) * 16 + r] = accw[i][g];
-    }
-  }
-  __syncthreads();
-  if (tid < 48) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int w8 = 0; w8 < 8; ++w8) {
-      t1 += red[(w8 * 48 + tid) * 2 + 0];
-      t2 += red[(w8 * 48 + tid) * 2 + 1];
-    }
-    partials[(size_t)blockIdx.x * 96 + 2 * tid + 0] = t1;
-    partials[(size_t)blockIdx.x * 96 + 2 * tid + 1] = (double)zistd[tid] * (t2 - (double)zmean[tid] * t1);
-  }
-}
-
-
-// =============================================================================== conv3x3 backward, one pass, weight gradient TAP-PACKED
-// Round 6.  conv3x3_bwd_fused_kernel's weight gradient deals the 27 (tap, 16 input channels) accumulator tiles of
-//     dW2[o][c][tap] = sum_p g[p][o] * zn[p + d_tap][c]
-// to 2 halves x 4 waves with the 12 output channels as the MFMA columns (12 of 16 used) and one of the 28 slots empty: 224
-// MFMAs per wave and 256-pixel tile, and its operand is the BN2(z) HALO tile (10 x 34 pixels, each read 9 times).  Here the
-// sum runs over the pixel p' = p + d that zn is taken at:
-//     dW2[(tap, o)][c] = sum_{p'} g[p' - d_tap][o] * zn[p'][c]
-// rows (tap, o) = 108 of 112 in 7 row tiles, columns c = 48 in 3: 21 accumulator tiles instead of 27; every wave keeps all 21
-// (84 registers) and takes the k-steps of its OWN tile row (32 pixels = 8 k-steps): 168 MFMAs per wave and tile, balanced,
-// against 224 (-25 %; the kernel: 330 against 386, -14.5 %).  The operand that needs neighbours is now g, whose halo tile the
-// data gradient stages anyway (a per-lane offset into it per row tile: ds_read_b32, as before); z is needed at the tile's own
-// 256 pixels only and is staged RAW (no halo: -25 % of the z loads and LDS writes): BN2's affine is one fma on the fragment, and
-// the data gradient's BatchNorm statistics read the same raw rows from LDS instead of a second time from L2 (6 x 16-byte
-// global loads per lane and tile gone).  The eight waves' accumulators are summed through LDS once, after the last tile (fixed
-// order): one partial row of 21 x 256 floats per workgroup (it was 2 x 27 x 256).  Data gradient, g staging and the phase
-// structure (A: data gradient, barrier, B: weight gradient with the data gradient's epilogue riding on it, barrier) are
-// conv3x3_bwd_fused_kernel's.
-// DROP: the staged g carries the layer's dropout mask / (1 - p), as in conv3x3_bwd_data_kernel (both gradients use it).
-// STORE_GF: as in conv3x3_bwd_fused_kernel; false (GF == NULL) drops g_store, w_own and the copy of the committed g kept for it.
+// launcher instantiates <.., false> when the caller passes GF == NULL (the default path: this kernel forms dW2 itself); false
+// drops g_store, w_own and the copy of the committed g kept for it.
 template <bool A16, bool DROP = false, bool STORE_GF = true>
 __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     const float* __restrict__ G, int ldg, int c0, const float* __restrict__ W2, const float* __restrict__ Z,
@@ -1084,7 +756,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
         const int gi = tap * 3 + s3;
         if (gi < 2) {
           g_load(gi);
-          // a compiler-level memory barrier: with no store left in this phase (round 4's kernel committed the z halo here) LLVM
+          // a compiler-level memory barrier: with no store in this phase LLVM
           // sank the second pair of staging loads from here to their use at the end of the phase -- an HBM round trip in
           // front of every tile's barrier (ISA: global_load at MFMA 150 of 162, s_waitcnt vmcnt(0) at 156)
           asm volatile("" ::: "memory");
@@ -1113,9 +785,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
     g_store(0);
     g_store(1);
     EML_C3_STAMP(0);
-#ifndef EML_C3_NOZWAIT   // experiment build: what the wait costs (stale z: wrong results)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the z tile has landed
-#endif
     eml::lds_barrier();          // this tile's z is in place (and g_l[cur ^ 1] complete)
     EML_C3_STAMP(1);
     // ------------------------------------------------------------------ phase B: weight gradient (144 / 192 MFMAs per wave; row tile 3 shared between the pair -- 168 each -- measured slower: 14 spills)
@@ -1147,10 +817,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd_fused_tp_kernel(
                          // with s_waitcnt vmcnt(0) -- issued in front of them, every tile waited out its own request here.
           const int t2 = nxt < ntiles ? nxt : tile;
           const int b2 = t2 / (ty_n * tx_n), rem2 = t2 - b2 * (ty_n * tx_n);
-#ifndef EML_C3_NOZDMA   // experiment build: no z traffic at all (wrong results)
 #pragma unroll
           for (int it = 0; it < kZI; ++it) z_dma(it, b2, (rem2 / tx_n) * kTH, (rem2 % tx_n) * kTW, cur ^ 1);
-#endif
           __builtin_amdgcn_sched_barrier(0);
         }
         const bool pin = 4 * (ks & 7) < (ks < 8 ? xl0 : xl1);
@@ -1382,14 +1050,11 @@ struct NarrowArgs {
   double* partials;    // [grid][Kp][2]: S1 of channels k_lo .. k_lo+11 (S2 slot = 0: it comes from the weight gradient)
   int Cin, k_lo, ldg;
 };
-// VEC (round 4): floats per lane of the x operand.  2 = round 1's float2 (lane i of a 32-channel group
-// carries channels 2i, 2i+1: a wave instruction reads 4 rows x 128 B); 4 = float4 over 64-channel groups (4 rows x 256 B):
-// half as many vector-memory instructions for the operand that is 80 % of this kernel's bytes.  The access-shape probe
-// (profiles/r04_row_access_probe_wgrad.txt) streams the float2 shape at 4.6-5.0 TB/s and the float4 shape at 5.5-5.9 at
-// k = 208 / 224 (2.7-2.95 against 3.4-3.65 with two workgroups per CU) -- but the kernel itself did not get faster with it
-// (see the launcher): kept as an A/B build (EML_W1_VEC=4), the float2 form runs.
-template <bool POOL, bool NARROW = false, int VEC = 2>
-__global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd_weight_kernel(
+// The x operand is a float2 per lane (lane i of a 32-channel group carries channels 2i, 2i+1: a wave instruction reads 4 rows
+// x 128 B).  A float4 over 64-channel groups streams faster in the access-shape probe but made the kernel no faster, and the
+// narrow variant spilled 39 registers with it (profiles/r04_ab_w1_vec.txt).
+template <bool POOL, bool NARROW = false>
+__global__ __launch_bounds__(256, NARROW ? 2 : 1) void conv1x1_bwd_weight_kernel(
     const float* __restrict__ X, int ldx, int P, int Hin, int Win, int Kp, const float* __restrict__ scale1,
     const float* __restrict__ shift1, const float* __restrict__ DY, int ld_dy, const float* __restrict__ Zr,
     int ld_z, const float* __restrict__ cA, const float* __restrict__ cB, const float* __restrict__ cC, int n_valid,
@@ -1401,9 +1066,8 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
   __shared__ __attribute__((aligned(16))) float dz_l[2][64 * 48];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, kk = lane >> 4;
-  static_assert(VEC == 2 || (VEC == 4 && !POOL), "float4 operand: dense layers only");
-  constexpr int GW = 16 * VEC;            // channels per group
-  constexpr int MAXG = VEC == 2 ? 3 : 2;  // groups per wave (Kp <= 384)
+  constexpr int GW = 32;    // channels per group
+  constexpr int MAXG = 3;   // groups per wave (Kp <= 384)
   const int ngroups = (Kp + GW - 1) / GW;
   // narrow pass: A fragments (rows = the 12 channels, k = o), BN1 affine of this lane's 4 channels, f64 statistics
   float nsk[4] = {0.f, 0.f, 0.f, 0.f}, ntk[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1417,17 +1081,17 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
     }
   }
 
-  float sv[MAXG][VEC], tv[MAXG][VEC];
+  float sv[MAXG][2], tv[MAXG][2];
   int coff[MAXG];
   bool gv[MAXG];
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {
     const int cg = wave + 4 * i;
-    const int ch = GW * cg + VEC * r;
+    const int ch = GW * cg + 2 * r;
     gv[i] = cg < ngroups && ch < Kp;
     coff[i] = gv[i] ? ch : 0;
 #pragma unroll
-    for (int t = 0; t < VEC; ++t) {
+    for (int t = 0; t < 2; ++t) {
       sv[i][t] = gv[i] ? scale1[ch + t] : 0.f;
       tv[i][t] = gv[i] ? shift1[ch + t] : 0.f;
     }
@@ -1439,9 +1103,8 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
   const int spix = tid >> 2, sq = tid & 3;
   __shared__ __attribute__((aligned(16))) float co_l[3 * 48];
   __shared__ float wn_l[NARROW ? 12 * 64 : 1];
-  constexpr bool CO_LDS = NARROW || VEC == 4;   // the float4 variant needs the registers for its accumulators
-  float4 sa_r[CO_LDS ? 1 : 3], sb_r[CO_LDS ? 1 : 3], sc_r[CO_LDS ? 1 : 3];   // plain variant: the affine in registers
-  if constexpr (CO_LDS) {
+  float4 sa_r[NARROW ? 1 : 3], sb_r[NARROW ? 1 : 3], sc_r[NARROW ? 1 : 3];   // plain variant: the affine in registers
+  if constexpr (NARROW) {
     if (tid < 48) {
       const bool v = tid < n_valid;
       co_l[tid] = v ? cA[tid] : 0.f;
@@ -1472,11 +1135,11 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
     }
   }
   __syncthreads();
-  f32x4 acc[MAXG][VEC][3];
+  f32x4 acc[MAXG][2][3];
 #pragma unroll
   for (int i = 0; i < MAXG; ++i)
 #pragma unroll
-    for (int t = 0; t < VEC; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int n = 0; n < 3; ++n) acc[i][t][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
@@ -1506,7 +1169,7 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
     for (int j = 0; j < 3; ++j) {
       const int col = 4 * (sq + 4 * j);
       float4 sa, sb, sc;
-      if constexpr (CO_LDS) {
+      if constexpr (NARROW) {
         sa = *reinterpret_cast<const float4*>(co_l + col);
         sb = *reinterpret_cast<const float4*>(co_l + 48 + col);
         sc = *reinterpret_cast<const float4*>(co_l + 96 + col);
@@ -1528,22 +1191,16 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
   // loads of UQ pixel-quads are issued back to back with no control flow between them.
   auto chunk_loop = [&](auto ngw_c) {
     constexpr int NGW = decltype(ngw_c)::value;
-#ifdef EML_WGRAD_DEEP   // experiment build: half-size batches, four buffers, three batches (24 pixels) in flight
-    constexpr int UQ = POOL ? 1 : 2;
-    constexpr int NBUF = POOL ? 2 : 4;
-#else
-    constexpr int UQ = POOL ? 1 : (VEC == 4 ? 2 : 4);   // pixel quads per batch (the same bytes in flight for both VEC)
+    constexpr int UQ = POOL ? 1 : 4;      // pixel quads per batch
     constexpr int NBUF = 2;
-#endif
     constexpr int NS = POOL ? 4 : 1;      // input pixels per output pixel
     constexpr int NB = 16 / UQ;           // operand batches per 64-pixel chunk (a multiple of NBUF)
     constexpr int AHEAD = NBUF - 1;       // batches requested ahead of their MFMAs
     // x operand of one batch: UNCONDITIONAL loads from clamped pixels (validity is applied when the value is
     // used); they are requested AHEAD of their MFMAs, across chunk boundaries -- issued right before
     // use they exposed an HBM round trip per batch (ISA: global_load; s_waitcnt vmcnt; v_mfma).
-    using xv_t = std::conditional_t<VEC == 2, float2, float4>;
-    xv_t xr[NBUF][UQ][NGW > 0 ? NGW : 1][NS];
-    auto load_batch = [&](int chunk, int q0, xv_t (&dst)[UQ][NGW > 0 ? NGW : 1][NS]) {
+    float2 xr[NBUF][UQ][NGW > 0 ? NGW : 1][NS];
+    auto load_batch = [&](int chunk, int q0, float2 (&dst)[UQ][NGW > 0 ? NGW : 1][NS]) {
 #pragma unroll
       for (int u = 0; u < UQ; ++u) {
         const int pc = min(chunk * 64 + 4 * (q0 + u) + kk, P - 1);
@@ -1559,7 +1216,7 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
         for (int i = 0; i < NGW; ++i)
 #pragma unroll
           for (int sub = 0; sub < NS; ++sub)
-            dst[u][i][sub] = *reinterpret_cast<const xv_t*>(xp + ((sub >> 1) * (size_t)Win + (sub & 1)) * ldx + coff[i]);
+            dst[u][i][sub] = *reinterpret_cast<const float2*>(xp + ((sub >> 1) * (size_t)Win + (sub & 1)) * ldx + coff[i]);
       }
     };
     stage_load(blockIdx.x);
@@ -1614,28 +1271,24 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
             }
 #pragma unroll
             for (int i = 0; i < NGW; ++i) {
-              float av[VEC];
+              float av[2];
 #pragma unroll
-              for (int t = 0; t < VEC; ++t) av[t] = 0.f;
+              for (int t = 0; t < 2; ++t) av[t] = 0.f;
 #pragma unroll
               for (int sub = 0; sub < NS; ++sub) {
-                const xv_t xv = xr[bi % NBUF][u][i][sub];
+                const float2 xv = xr[bi % NBUF][u][i][sub];
                 av[0] += fmaxf(fmaf(xv.x, sv[i][0], tv[i][0]), 0.f);
                 av[1] += fmaxf(fmaf(xv.y, sv[i][1], tv[i][1]), 0.f);
-                if constexpr (VEC == 4) {
-                  av[2] += fmaxf(fmaf(xv.z, sv[i][2], tv[i][2]), 0.f);
-                  av[3] += fmaxf(fmaf(xv.w, sv[i][3], tv[i][3]), 0.f);
-                }
               }
 #pragma unroll
-              for (int t = 0; t < VEC; ++t) {
+              for (int t = 0; t < 2; ++t) {
                 if constexpr (POOL) av[t] *= 0.25f;
                 if (!pvu) av[t] = 0.f;
               }
 #pragma unroll
               for (int n = 0; n < 3; ++n)
 #pragma unroll
-                for (int t = 0; t < VEC; ++t) acc[i][t][n] = mfma16(av[t], bz[n], acc[i][t][n]);
+                for (int t = 0; t < 2; ++t) acc[i][t][n] = mfma16(av[t], bz[n], acc[i][t][n]);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -1678,10 +1331,10 @@ __global__ __launch_bounds__(256, (NARROW || VEC == 4) ? 2 : 1) void conv1x1_bwd
   for (int i = 0; i < MAXG; ++i) {
     const int cg = wave + 4 * i;
 #pragma unroll
-    for (int t = 0; t < VEC; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int ch = GW * cg + VEC * (4 * kk + g) + t;  // D row 4kk+g of tile t
+        const int ch = GW * cg + 2 * (4 * kk + g) + t;  // D row 4kk+g of tile t
         if (cg < ngroups && ch < Kp) {
 #pragma unroll
           for (int n = 0; n < 3; ++n) out[(size_t)ch * 48 + 16 * n + r] = acc[i][t][n][g];
@@ -3046,38 +2699,48 @@ __global__ __launch_bounds__(256) void bn_dgamma_direct_reduce_kernel(const doub
 }
 
 // =============================================================================== C ABI
+// conv3x3_bwd_data_kernel behind both entries below.  DROP: with the layer's dropout mask (seed, layer, p), which needs the
+// fused affine (X).  16-byte staging (WIDE) where every slice it touches is 16-byte aligned.
+template <bool DROP>
+static int conv3x3_bwd_data_launch(const char* name, const float* G, int ldg, int c0, const float* W2, const float* Z,
+                                   const float* zmean, const float* zistd, float* DZ, int B, int H, int W, double* partials,
+                                   int grid, const float* X, int ldx, int cx, const float* sB, const float* sC, float* GF,
+                                   unsigned long long seed, int layer, double p, eml_stream_t stream) {
+  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || (c0 & 1) ||
+      (ldg & 1))
+    return eml::fail(EML_EINVAL, "%s: bad arguments", name);
+  if (DROP || X) {
+    if (!X || !sB || !sC || !GF || (ldx & 1)) return eml::fail(EML_EINVAL, "%s: fused affine needs X, sB, sC, GF", name);
+    if (cx < 0 || (cx & 1)) return eml::fail(EML_EINVAL, "%s: cx must be even", name);
+  }
+  eml::DropKey dk{};
+  if constexpr (DROP) {
+    if (!(p >= 0.0 && p <= 1.0) || layer < 0)
+      return eml::fail(EML_EINVAL, "%s: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", name, p, layer);
+    if ((long long)B * H * W > 0x7FFFFFFFll) return eml::fail(EML_EINVAL, "%s: B*H*W must fit the 32-bit pixel counter", name);
+    dk = eml_drop_key(seed, layer, p);
+  }
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const bool wide = (ldg & 3) == 0 && (c0 & 3) == 0 && al16(G) &&
+                    (!X || ((ldx & 3) == 0 && (cx & 3) == 0 && al16(X) && al16(sB) && al16(sC) && al16(GF)));
+#define EML_LAUNCH_D3(FUSEV, WIDEV)                                                                                      \
+  hipLaunchKernelGGL((conv3x3_bwd_data_kernel<FUSEV, WIDEV, DROP>), dim3(grid), dim3(kBD), 0, (hipStream_t)stream, G, ldg, c0, \
+                     W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, dk)
+  if (DROP || X) {
+    if (wide) EML_LAUNCH_D3(true, true); else EML_LAUNCH_D3(true, false);
+  } else if constexpr (!DROP) {
+    if (wide) EML_LAUNCH_D3(false, true); else EML_LAUNCH_D3(false, false);
+  }
+#undef EML_LAUNCH_D3
+  return eml::check_launch(name);
+}
+
 extern "C" int eml_dense_conv3x3_bwd_data_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
                                               const float* zmean, const float* zistd, float* DZ, int B, int H, int W,
                                               double* partials, int grid, const float* X, int ldx, int cx,
                                               const float* sB, const float* sC, float* GF, eml_stream_t stream) {
-  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || (c0 & 1) ||
-      (ldg & 1))
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_f32: bad arguments");
-  if (X) {
-    if (!sB || !sC || !GF || (ldx & 1))
-      return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_f32: fused affine needs X, sB, sC, GF");
-    if (cx < 0 || (cx & 1)) return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_f32: cx must be even");
-  }
-  // 16-byte staging where every slice it touches is 16-byte aligned (EML_D3_NARROW=1: the float2 path, for the A/B);
-  // 8-row tiles / 512 threads / one workgroup per CU; EML_D3_SHORT=1: the 4-row / 256-thread / two-per-CU geometry of the
-  // round-4 A/B (15.34 against 14.43 ms per step: slower, profiles/r04_ab_conv3x3.txt)
-  static const bool narrow = [] { const char* v = getenv("EML_D3_NARROW"); return v && v[0] == '1'; }();
-  static const bool tall = [] { const char* v = getenv("EML_D3_SHORT"); return !(v && v[0] == '1'); }();
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool wide = !narrow && (ldg & 3) == 0 && (c0 & 3) == 0 && al16(G) &&
-                    (!X || ((ldx & 3) == 0 && (cx & 3) == 0 && al16(X) && al16(sB) && al16(sC) && al16(GF)));
-#define EML_LAUNCH_D3(FUSEV, WIDEV, THV)                                                                                \
-  hipLaunchKernelGGL((conv3x3_bwd_data_kernel<FUSEV, WIDEV, THV>), dim3(grid), dim3(THV * 64), 0, (hipStream_t)stream, G, ldg, \
-                     c0, W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, eml::DropKey{})
-  if (X) {
-    if (tall) { if (wide) EML_LAUNCH_D3(true, true, 8); else EML_LAUNCH_D3(true, false, 8); }
-    else      { EML_LAUNCH_D3(true, false, 4); }   // (the 16-byte staging spills 18 registers next to the fused affine here)
-  } else {
-    if (tall) { if (wide) EML_LAUNCH_D3(false, true, 8); else EML_LAUNCH_D3(false, false, 8); }
-    else      { if (wide) EML_LAUNCH_D3(false, true, 4); else EML_LAUNCH_D3(false, false, 4); }
-  }
-#undef EML_LAUNCH_D3
-  return eml::check_launch("eml_dense_conv3x3_bwd_data_f32");
+  return conv3x3_bwd_data_launch<false>("eml_dense_conv3x3_bwd_data_f32", G, ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W, partials,
+                                        grid, X, ldx, cx, sB, sC, GF, 0, 0, 0.0, stream);
 }
 
 extern "C" int eml_dense_conv3x3_bwd_data_drop_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
@@ -3085,31 +2748,8 @@ extern "C" int eml_dense_conv3x3_bwd_data_drop_f32(const float* G, int ldg, int 
                                                    double* partials, int grid, const float* X, int ldx, int cx,
                                                    const float* sB, const float* sC, float* GF, unsigned long long seed,
                                                    int layer, double p, eml_stream_t stream) {
-  if (!G || !W2 || !Z || !zmean || !zistd || !DZ || !partials || B < 1 || H < 1 || W < 1 || grid < 1 || (c0 & 1) ||
-      (ldg & 1))
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: bad arguments");
-  if (!X || !sB || !sC || !GF || (ldx & 1))
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: fused affine needs X, sB, sC, GF");
-  if (cx < 0 || (cx & 1)) return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: cx must be even");
-  if (!(p >= 0.0 && p <= 1.0) || layer < 0)
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: p must be in [0, 1] and layer >= 0 (p = %g, layer = %d)", p,
-                     layer);
-  if ((long long)B * H * W > 0x7FFFFFFFll)
-    return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_data_drop_f32: B*H*W must fit the 32-bit pixel counter");
-  // the geometry choice of eml_dense_conv3x3_bwd_data_f32 (with X)
-  static const bool narrow = [] { const char* v = getenv("EML_D3_NARROW"); return v && v[0] == '1'; }();
-  static const bool tall = [] { const char* v = getenv("EML_D3_SHORT"); return !(v && v[0] == '1'); }();
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool wide = !narrow && (ldg & 3) == 0 && (c0 & 3) == 0 && al16(G) && (ldx & 3) == 0 && (cx & 3) == 0 && al16(X) &&
-                    al16(sB) && al16(sC) && al16(GF);
-  const eml::DropKey dk = eml_drop_key(seed, layer, p);
-#define EML_LAUNCH_D3(WIDEV, THV)                                                                                       \
-  hipLaunchKernelGGL((conv3x3_bwd_data_kernel<true, WIDEV, THV, true>), dim3(grid), dim3(THV * 64), 0, (hipStream_t)stream, G, \
-                     ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, dk)
-  if (tall) { if (wide) EML_LAUNCH_D3(true, 8); else EML_LAUNCH_D3(false, 8); }
-  else      { EML_LAUNCH_D3(false, 4); }
-#undef EML_LAUNCH_D3
-  return eml::check_launch("eml_dense_conv3x3_bwd_data_drop_f32");
+  return conv3x3_bwd_data_launch<true>("eml_dense_conv3x3_bwd_data_drop_f32", G, ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W,
+                                       partials, grid, X, ldx, cx, sB, sC, GF, seed, layer, p, stream);
 }
 
 extern "C" int eml_dense_conv3x3_bwd_weight_f32(const float* G, int ldg, int c0, const float* Z, const float* scale2,
@@ -3117,9 +2757,9 @@ extern "C" int eml_dense_conv3x3_bwd_weight_f32(const float* G, int ldg, int c0,
                                                 int grid, eml_stream_t stream) {
   if (!G || !Z || !scale2 || !shift2 || !partial || !dW2 || B < 1 || H < 1 || W < 1 || grid < 1)
     return eml::fail(EML_EINVAL, "eml_dense_conv3x3_bwd_weight_f32: bad arguments");
-  // 16-byte loads of the 12-channel slice need ldg and c0 multiples of 4 (always true for the engine's buffers)
-  static const bool greg = [] { const char* v = getenv("EML_W3_GREG"); return v && v[0] == '1'; }();
-  if (!greg && (ldg & 3) == 0 && (c0 & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 15) == 0) {
+  // the g operand through LDS needs 16-byte loads of the 12-channel slice (ldg and c0 multiples of 4: always true for the
+  // engine's buffers); GLDS = false is the fallback for unaligned slices
+  if ((ldg & 3) == 0 && (c0 & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 15) == 0) {
     const size_t lds = (size_t)(2 * kHH * kHW * kPSW + 2 * kGL) * sizeof(float);
     EML_ENSURE_LDS((&conv3x3_bwd_weight_kernel<true>), lds);
     hipLaunchKernelGGL(conv3x3_bwd_weight_kernel<true>, dim3(grid), dim3(kBW), lds, (hipStream_t)stream, G, ldg, c0, Z,
@@ -3147,12 +2787,12 @@ extern "C" int eml_c3_read_stamps(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-// One launch for the pair above (see conv3x3_bwd_fused_kernel).  Returns EML_EINVAL when the buffers do not allow the
-// 16-byte staging (the caller then issues the two separate launches).
+// One launch for the pair above (conv3x3_bwd_fused_tp_kernel).  0: the buffers do not allow its staging (the caller then issues
+// the two separate launches).
 extern "C" int eml_dense_conv3x3_bwd_fused_supported(int ldg, int c0, int ldx, int cx) {
   return ((ldg & 1) == 0 && (c0 & 1) == 0 && (ldx & 1) == 0 && (cx & 1) == 0) ? 1 : 0;
 }
-// one launch for the pair above (see conv3x3_bwd_fused_kernel); DROP: with the layer's dropout mask (dk)
+// DROP: with the layer's dropout mask (dk)
 template <bool DROP>
 static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, int c0, const float* W2, const float* Z,
                                     const float* zmean, const float* zistd, float* DZ, int B, int H, int W, double* partials,
@@ -3167,66 +2807,20 @@ static int conv3x3_bwd_fused_launch(const char* name, const float* G, int ldg, i
       !al16(shift2))
     return eml::fail(EML_EINVAL, "%s: needs even ldg, c0, ldx, cx and 16-byte aligned buffers", name);
   const bool a16 = (ldg & 3) == 0 && (c0 & 3) == 0 && (ldx & 3) == 0 && (cx & 3) == 0;
-#ifndef EML_C3_WTP   // experiment builds (tools/exp_build.sh nowtp -DEML_C3_WTP=0): round 4's weight gradient (27 tiles, z halo)
-#define EML_C3_WTP 1
-#endif
-#if EML_C3_WTP
   const size_t lds = (size_t)(2 * kHH * kHW * kPSG + 2 * kTH * kTW * 48 + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);   // 163 392 of 163 840 bytes
-  if (a16) {
-    if (GF) {
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP, true>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    } else {   // nobody reads GF: no store (see STORE_GF)
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<true, DROP, false>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<true, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    }
-  } else {
-    if (GF) {
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP, true>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    } else {   // nobody reads GF: no store (see STORE_GF)
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_tp_kernel<false, DROP, false>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_tp_kernel<false, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z,
-                         zmean, zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    }
-  }
+  const auto launch = [&](auto a16_c, auto gf_c) {   // GF == NULL: nobody reads it, no store (see STORE_GF)
+    const auto kernel = &conv3x3_bwd_fused_tp_kernel<decltype(a16_c)::value, DROP, decltype(gf_c)::value>;
+    EML_ENSURE_LDS(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean, zistd, DZ, B, H, W,
+                       partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
+  };
+  if (a16) { if (GF) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+  else     { if (GF) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
   int rc = eml::check_launch(name);
   if (rc) return rc;
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(21 * 256 / 64), dim3(256), 0, (hipStream_t)stream, partialW, grid,
                      (size_t)21 * 256, 3, 0, 0, 0, dW2);
   return eml::check_launch(DROP ? "eml_dense_conv3x3_bwd_fused_drop_f32(reduce)" : "eml_dense_conv3x3_bwd_fused_f32(reduce)");
-#else
-  const size_t lds = (size_t)(2 * kHH * kHW * kPSG + kHH * kHW * kPSW + 27 * 3 * 64 + 32) * sizeof(float) + 8 * 48 * 2 * sizeof(double);
-  if (a16) {
-    if (GF) {
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP, true>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    } else {   // nobody reads GF: no store (see STORE_GF)
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<true, DROP, false>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<true, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    }
-  } else {
-    if (GF) {
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP, true>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    } else {   // nobody reads GF: no store (see STORE_GF)
-      EML_ENSURE_LDS((&conv3x3_bwd_fused_kernel<false, DROP, false>), lds);
-      hipLaunchKernelGGL((conv3x3_bwd_fused_kernel<false, DROP, false>), dim3(grid), dim3(512), lds, (hipStream_t)stream, G, ldg, c0, W2, Z, zmean,
-                         zistd, DZ, B, H, W, partials, X, ldx, cx, sB, sC, GF, scale2, shift2, partialW, dk);
-    }
-  }
-  int rc = eml::check_launch(name);
-  if (rc) return rc;
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(27 * 256 / 64), dim3(256), 0, (hipStream_t)stream, partialW, 2 * grid,
-                     (size_t)27 * 256, 1, 0, 0, 0, dW2);
-  return eml::check_launch(DROP ? "eml_dense_conv3x3_bwd_fused_drop_f32(reduce)" : "eml_dense_conv3x3_bwd_fused_f32(reduce)");
-#endif
 }
 
 extern "C" int eml_dense_conv3x3_bwd_fused_f32(const float* G, int ldg, int c0, const float* W2, const float* Z,
@@ -3341,22 +2935,8 @@ extern "C" int eml_dense_conv1x1_bwd_weight_f32(const float* X, int ldx, long P,
     if (n_load > 48) n_load = 48;
     if (n_load < nv) return eml::fail(EML_EINVAL, "eml_dense_conv1x1_bwd_weight_f32: DY/Zr rows narrower than Cout");
     const NarrowArgs na{W1, G, N12, partials_n, Cin, k_lo, ldg};
-    // float4 x operand: A/B only (EML_W1_VEC=4).  Measured (profiles/r04_ab_w1_vec.txt): on the layers where its 64-channel
-    // groups deal evenly (Kp in [160, 256], the plain variant) 30.4 against 29.95-30.4 ms per step -- no gain, although the
-    // access-shape probe streams the float4 shape 19-24 % faster: the x stream's shape is not what bounds this kernel.
-    // Everywhere (uneven deals, the narrow variant spilling 39 registers): 34.6 ms.
-    static const int vec_env = [] { const char* v = getenv("EML_W1_VEC"); return v ? atoi(v) : 0; }();
-    const bool vec4 = !pool && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-                      vec_env == 4;
-    if (vec4 && N12 && vec_env == 4)   // (the narrow epilogue + float4 operand spills 39 registers: A/B only)
-      hipLaunchKernelGGL((conv1x1_bwd_weight_kernel<false, true, 4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, X, ldx,
-                         (int)P, Hin, Win, Kp, scale1, shift1, DY + n0, ld_dy, Zr + n0, ld_z, cA + n0, cB + n0, cC + n0,
-                         nv, n_load, partial, dz_out, na);
-    else if (vec4 && !N12)
-      hipLaunchKernelGGL((conv1x1_bwd_weight_kernel<false, false, 4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, X, ldx,
-                         (int)P, Hin, Win, Kp, scale1, shift1, DY + n0, ld_dy, Zr + n0, ld_z, cA + n0, cB + n0, cC + n0,
-                         nv, n_load, partial, dz_out, na);
-    else if (pool)
+    // (the x operand as float4 over 64-channel groups measured no gain: profiles/r04_ab_w1_vec.txt)
+    if (pool)
       hipLaunchKernelGGL((conv1x1_bwd_weight_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, X, ldx,
                          (int)P, Hin, Win, Kp, scale1, shift1, DY + n0, ld_dy, Zr + n0, ld_z, cA + n0, cB + n0, cC + n0,
                          nv, n_load, partial, nullptr, na);

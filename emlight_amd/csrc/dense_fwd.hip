@@ -28,15 +28,10 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// component t of a float4 (t is a compile-time constant after unrolling).  MFMA loops run t OUTERMOST so
-// that consecutive MFMAs hit different accumulators: back-to-back MFMAs on one accumulator pay the
-// 40-cycle dependent latency instead of the 32-cycle issue interval (MI355X_MICROARCH.md).
-__device__ __forceinline__ float f4c(const float4& v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
+using eml::f32x4;
+using eml::f4c;
+using eml::mfma16;
+using eml::shfl_xor_d;
 
 __device__ __forceinline__ float4 bn_relu4(float4 x, float4 s, float4 t) {
   float4 r;
@@ -46,8 +41,6 @@ __device__ __forceinline__ float4 bn_relu4(float4 x, float4 s, float4 t) {
   r.w = fmaxf(fmaf(x.w, s.w, t.w), 0.f);
   return r;
 }
-
-__device__ __forceinline__ double shfl_xor_d(double v, int m) { return __shfl_xor(v, m, 64); }
 
 // Reduce per-lane f64 (sum, sumsq) of NCH channels-per-lane over the 4 row groups of a wave
 // and the 4 waves of a block; channel of (n, lane) is 16n + (lane & 15).
@@ -74,11 +67,8 @@ __device__ __forceinline__ void block_stats_store(double (&s)[NT], double (&q)[N
 // ------------------------------------------------------------------------------ conv1x1
 // out[p][n0 + o] (o < n_valid <= 48) for output pixels p < P.  POOL: the A operand is the
 // 2x2 average of relu(bn(x)) (avg-pool commutes with the 1x1 conv: transition, DenseNet.py:14-21).
-#ifndef EML_FWD_MIN_WG   // experiment builds only (tools/exp_build.sh): workgroups per CU the register allocation is capped for
-#define EML_FWD_MIN_WG 2
-#endif
 template <bool POOL, bool MASK = false /* emit the ReLU ballot words (relu_mask != NULL, dense layers in training) */>
-__global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
+__global__ __launch_bounds__(256, 2) void conv1x1_fwd_kernel(
     const float* __restrict__ X, int ldx, int P, int Hin, int Win, int Kp,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ Wp,
     float* __restrict__ out, int ldo, int n_valid, double* __restrict__ partials,
@@ -109,20 +99,15 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
     sl[e] = scale[e];
     tl[e] = shift[e];
   }
-#ifdef EML_FWD_STATS_LDS   // experiment build: the 24 f64 statistics accumulators in wave-private LDS slots (48 registers less)
-  for (int e = tid; e < 4 * 48 * 2; e += 256) red[e] = 0.0;
-#endif
   __syncthreads();
 
   // D^T form (weights as the MFMA A operand): lane (r, kk) owns output channels 16n + 4kk .. +3 of pixel
   // p0 + 16m + r -> 16-byte stores; per-lane statistics of those 12 channels.
-#ifndef EML_FWD_STATS_LDS
   double ssum[3][4], ssq[3][4];
 #pragma unroll
   for (int n = 0; n < 3; ++n)
 #pragma unroll
     for (int g = 0; g < 4; ++g) ssum[n][g] = ssq[n][g] = 0.0;
-#endif
   const int nj = Kp >> 4;
   const int ntiles = (P + 255) >> 8;
   const int Wo = Win >> 1, Ho = Hin >> 1;
@@ -191,7 +176,6 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
         __builtin_amdgcn_sched_barrier(0);  // the scheduler otherwise sinks these requests below the MFMAs
 #pragma unroll
         for (int m = 0; m < 4; ++m) a[m] = bn_relu4(xc[m], s4, t4);
-#ifndef EML_FWD_NOMASK   // experiment build (tools/exp_build.sh nomask -DEML_FWD_NOMASK): what the ballots + 16 selects + the store cost
         if constexpr (MASK) {
           // ReLU mask of this K-step as wave ballots: word (pixel group, K-step, t), bit r + 16*kk <-> pixel 16*pg + r,
           // channel 16*j + 4*kk + t -- the lane layout of the data-gradient kernel, which then needs neither X nor
@@ -208,7 +192,6 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
             }
           if (lane < 16) mask_l[((wave * 4 + (lane >> 2)) * nj + j) * 4 + (lane & 3)] = mine;
         }
-#endif
       }
       float4 bw[3];
 #pragma unroll
@@ -264,17 +247,8 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-#ifdef EML_FWD_STATS_LDS
-        const float t1 = eml::row16_sum(ls[g]), t2 = eml::row16_sum(lq[g]);
-        if (r == 0) {
-          double* d = red + (wave * 48 + 16 * n + 4 * kk + g) * 2;
-          d[0] += (double)t1;
-          d[1] += (double)t2;
-        }
-#else
         ssum[n][g] += (double)ls[g];
         ssq[n][g] += (double)lq[g];
-#endif
       }
     }
     if (staged) {
@@ -300,7 +274,6 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
     }
   }
   // channel statistics: over the 16 pixel lanes r, then the 4 waves
-#ifndef EML_FWD_STATS_LDS
 #pragma unroll
   for (int n = 0; n < 3; ++n)
 #pragma unroll
@@ -315,7 +288,6 @@ __global__ __launch_bounds__(256, EML_FWD_MIN_WG) void conv1x1_fwd_kernel(
         red[(wave * 48 + 16 * n + 4 * kk + g) * 2 + 1] = ssq[n][g];
       }
     }
-#endif
   __syncthreads();
   for (int e = tid; e < 96; e += 256)
     partials[(size_t)blockIdx.x * 96 + e] = (red[e] + red[96 + e]) + (red[192 + e] + red[288 + e]);
@@ -1251,13 +1223,12 @@ extern "C" int eml_dense_conv1x1_fwd_f32(const float* X, int ldx, long P, int Hi
   if (relu_mask && (pool || Cout > 48))
     return eml::fail(EML_EINVAL, "eml_dense_conv1x1_fwd_f32: relu_mask is for dense layers (no pool, Cout <= 48)");
   if (pool && ((Hin & 1) || (Win & 1))) return eml::fail(EML_EINVAL, "eml_dense_conv1x1_fwd_f32: pool needs even H, W");
-  // dense layers with a compact 48-wide output leave through a staging tile (whole-line stores): EML_FWD_STAGED=0 for the A/B
-  static const bool staged_env = [] { const char* v = getenv("EML_FWD_STAGED"); return !(v && v[0] == '0'); }();
   const size_t lds0 = ((size_t)Kp * 48 + 2 * Kp) * sizeof(float) + 4 * 48 * 2 * sizeof(double) +
                       (relu_mask ? (size_t)4 * 16 * (Kp / 16) * sizeof(unsigned long long) : 0);
   const size_t stg_bytes = (size_t)4 * 16 * 52 * sizeof(float);
-  // (only where two workgroups per CU still fit with the tile: the widest layers of blocks 2 and 3 keep the direct stores)
-  const int staged = (staged_env && !pool && Cout == 48 && ldo == 48 && (reinterpret_cast<size_t>(out) & 15) == 0 &&
+  // dense layers with a compact 48-wide output leave through a staging tile (whole-line stores, profiles/r06_write_pattern.txt),
+  // where two workgroups per CU still fit with the tile: the widest layers of blocks 2 and 3 keep the direct stores
+  const int staged = (!pool && Cout == 48 && ldo == 48 && (reinterpret_cast<size_t>(out) & 15) == 0 &&
                       lds0 + stg_bytes <= 80 * 1024) ? 1 : 0;
   const size_t lds = lds0 + (staged ? stg_bytes : 0);
   if (lds > 160 * 1024) return eml::fail(EML_EINVAL, "eml_dense_conv1x1_fwd_f32: Kp=%d does not fit LDS", Kp);

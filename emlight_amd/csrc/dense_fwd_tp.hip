@@ -30,12 +30,9 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float f4c(const float4& v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
+using eml::f32x4;
+using eml::f4c;
+using eml::mfma16;
 
 constexpr int kNWMax = 4;
 

@@ -73,6 +73,17 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// ---- f32 MFMA 16x16x4 and its fragment helpers (the dense encoder's kernels)
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// component t of a float4 (t is a compile-time constant after unrolling).  MFMA loops run t OUTERMOST so
+// that consecutive MFMAs hit different accumulators: back-to-back MFMAs on one accumulator pay the
+// 40-cycle dependent latency instead of the 32-cycle issue interval (MI355X_MICROARCH.md).
+__device__ __forceinline__ float f4c(const float4& v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
+__device__ __forceinline__ double shfl_xor_d(double v, int m) { return __shfl_xor(v, m, 64); }
+
 // ---- DPP cross-lane moves (VALU, no LDS round trip).  hipcc lowers __shfl_xor to ds_bpermute_b32 + an
 // lgkmcnt(0) wait per step; inside an MFMA epilogue that serialises thousands of cycles (ISA of the
 // conv1x1 dgrad: 32 dependent bpermutes per 16-channel tile).  Control words: quad_perm [1,0,3,2] = 0xB1,

@@ -355,10 +355,10 @@ int eml_dense_conv3x3_bwd_data_f32(const float* G, int ldg, int c0, const float*
                                    int W, double* partials, int grid, const float* X, int ldx, int cx,
                                    const float* sB, const float* sC, float* GF, eml_stream_t stream);
 
-/* The two launches around this comment as ONE pass over the tiles (round 4): the data gradient with the fused BN1 affine
+/* The two launches around this comment as ONE pass over the tiles: the data gradient with the fused BN1 affine
  * (X, sB, sC, GF as in eml_dense_conv3x3_bwd_data_f32 with X != NULL) and the weight gradient of the same layer,
  * dW2 = sum_p g[p] (x) (scale2*Z + shift2)[p+tap], on the g tile the data gradient has just staged (autograd of
- * DenseNet.py:38-43: conv2's backward w.r.t. its input and its weight).  Round 6: the weight gradient is summed over the
+ * DenseNet.py:38-43: conv2's backward w.r.t. its input and its weight).  The weight gradient is summed over the
  * pixel the BN2(z) operand is taken at, with the 9 taps x 12 output channels as the MFMA rows (21 accumulator tiles instead
  * of 27; z at the tile's own pixels only, csrc/dense_bwd.hip: conv3x3_bwd_fused_tp_kernel).
  * Needs even ldg, c0, ldx, cx and 16-byte aligned buffers (eml_dense_conv3x3_bwd_fused_supported; otherwise EML_EINVAL:

@@ -21,8 +21,6 @@ run ov EML_WGRAD_OVERLAP=1
 run ov_s128 EML_WGRAD_OVERLAP=1 EML_GRID3_SIDE=128
 run ov_s64_g384 EML_WGRAD_OVERLAP=1 EML_GRID3_SIDE=64 EML_GRID=384
 run ov_s64 EML_WGRAD_OVERLAP=1 EML_GRID3_SIDE=64
-run ov_lo EML_WGRAD_OVERLAP=1 EML_SIDE_PRIO=1
-run ov_hi EML_WGRAD_OVERLAP=1 EML_SIDE_PRIO=-1
 run base2 EML_WGRAD_OVERLAP=0
 EML_WGRAD_OVERLAP=1 timeout 600 python -m pytest $REPO/tests/test_gpu_densenet.py -x -q 2>&1 | tail -3
 rm -rf /tmp/ovt

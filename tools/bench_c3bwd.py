@@ -1,5 +1,5 @@
 """conv3x3 backward, fused data + weight gradient (eml_dense_conv3x3_bwd_fused_f32) at the encoder's block geometries;
-EML_LIB_PATH selects an experiment build (tools/exp_build.sh nowtp -DEML_C3_WTP=0: round 4's weight gradient)."""
+EML_LIB_PATH selects an experiment build (tools/exp_build.sh)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
