@@ -5,6 +5,7 @@
 The sampling pattern (``cal_index``/``gen_grid_coordinates``, ``:31-84``) depends only on (H, W, stride):
 it is built once, vectorised in float64 numpy (the reference loops H*W times in Python), and cached.
 """
+from collections import namedtuple
 from functools import lru_cache
 
 import numpy as np
@@ -13,7 +14,7 @@ import torch
 from torch import nn
 from torch.nn.parameter import Parameter
 
-from .._knobs import knob_choice, knob_flag, knob_int
+from .._knobs import knob_flag, knob_int
 
 
 @lru_cache(None)
@@ -222,9 +223,9 @@ def _lowres_plan(geo, B, C, O, transposed=False):
     return fp, fp_max, split, lidx
 
 
-def _lowres_conv(xr, idx, wgt, rowmax, ke, plan, w2, bias, res, slope, B, n_src, n_dst, C, O):
-    """One call of ``eml_sphere_conv_lowres_f32``: (B * n_dst, O) = act(gather(xr) W2^T + bias + res).  (``idx``: the raw table the
-    plan's footprint-local one was made from -- kept in the signature for the callers' symmetry, the kernel takes the plan's.)"""
+def _lowres_conv(xr, wgt, rowmax, ke, plan, w2, bias, res, slope, B, n_src, n_dst, C, O):
+    """One call of ``eml_sphere_conv_lowres_f32`` over the plan's footprint-local table: (B * n_dst, O) = act(gather(xr) W2^T +
+    bias + res)."""
     from .. import _lib
     L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
     fp, fp_max, split, idx = plan
@@ -236,10 +237,74 @@ def _lowres_conv(xr, idx, wgt, rowmax, ke, plan, w2, bias, res, slope, B, n_src,
     return y
 
 
+def _w2_of(weight):
+    """(O, C, 3, 3) -> the (O, 9C) operand with columns ordered (tap, c) like A9: a view where the memory already is (O, 3, 3, C)."""
+    return weight.permute(0, 2, 3, 1).reshape(weight.shape[0], -1)
+
+
+def _w2_as_weight(w2, C):
+    """The inverse view: a (O, 9C) operand -- or weight gradient -- in (tap, c) column order as a (O, C, 3, 3) tensor."""
+    return w2.view(-1, 3, 3, C).permute(0, 3, 1, 2)
+
+
+# which of a SphereConv's inputs take a gradient
+_Needs = namedtuple("_Needs", "x weight bias residual")
+# the kernels of one SphereConv layer (``_conv_plan``).  ``fwd`` / ``dgrad`` / ``wgrad``: "narrow", "small", "lowres" (never a
+# weight gradient), "fused" or "library" (im2col + GEMM; dY W2 + col2im), None for a gradient nobody needs; ``keep``: the forward
+# leaves its im2col operand behind for the library weight gradient; ``split``: K-split of the fused weight gradient (else 0)
+_ConvPlan = namedtuple("_ConvPlan", "fwd dgrad wgrad keep split")
+
+
+def _operand_units(B, po, C, units):
+    """Is the would-be im2col operand A9 (B * po, 9C) f32 at least ``units`` times ``SphereConv2D.fused_min_bytes``?"""
+    return B * po * 9 * C * 4 >= units * SphereConv2D.fused_min_bytes
+
+
+def _conv_plan(kind, stride, B, C, O, H, W, has_res, slope, needs, small_ok, narrow_ok, lowres=(False, False), fwd=None):
+    """Every per-shape choice of a SphereConv layer, in priority order -> ``_ConvPlan``.  Pure host arithmetic: ``small_ok`` /
+    ``narrow_ok`` are ``eml_sphere_conv_small_supported(C, O)`` / ``eml_sphere_conv_narrow_supported(C, O)``; ``lowres``:
+    (forward, input gradient) the footprint kernel was asked for AND supports (``SphereConv2D.lowres``, ``_lowres_plan``);
+    ``fwd``: the forward the caller runs itself (the one-launch SPADE: "fused").  Measured per shape: tools/sphere_layers.py,
+    profiles/r02_sphere_layers.jsonl."""
+    po = -(-H // stride) * -(-W // stride)
+    lim = SphereConv2D.fused_min_bytes
+    if B <= 0:
+        fwd = dgrad = wgrad = "library"                  # nothing to launch: ATen's empty GEMMs
+    elif not has_res and small_ok:
+        # 3-channel input layers (SPADE's mlp_shared 3 -> 128, VGG's 3 -> 64; not the discriminator's 6 -> 64): bound by the
+        # write of their output -- one pass each way with the activation (and its backward, and the bias gradient) folded in
+        fwd = dgrad = wgrad = "small"
+    elif not has_res and slope == 1.0 and kind != "planar" and narrow_ok:
+        # few-channel OUTPUT layers (conv_img 64 -> 3, the discriminators' final convolutions): one-pass kernels, no 9x operand
+        fwd = dgrad = wgrad = "narrow"
+    else:
+        # forward: the fused kernels run at 85-115 TF/s; im2col + the library GEMM is faster only where the GEMM is wide
+        # (O >= 512) and the operand small -- there the library's 115-125 TF/s wins and A9 costs little memory
+        if fwd is None:
+            fused = C % 32 == 0 and O % 64 == 0 and (_operand_units(B, po, C, 32) or (O <= 256 and _operand_units(B, po, C, 1)))
+            fwd = "lowres" if lowres[0] else "fused" if fused else "library"
+        # input gradient: the forward kernel on the transposed tap table (K = 9*O, N = C) beats dY W2 (library) + col2im where
+        # the pixel count is large and O <= 256; wide heads (K = 9*O >= 4608) stay unfused
+        fused = O % 32 == 0 and C % 64 == 0 and stride == 1 and (lim == 0 or (O <= 256 and B * po >= 131072))
+        dgrad = "lowres" if lowres[1] else "fused" if fused else "library"
+        # weight gradient: K = pixels; below ~32k pixels the split-K tiles are short and the library's long-K GEMM wins.  Where
+        # the forward left A9 behind (wide heads, O >= 512) it is ONE long-K library GEMM on it -- 145-152 TF/s on the recorded
+        # selection (_gemm_selection.py) against the fused kernel's 110, with no gather pass of its own
+        fused = (C % 64 == 0 and O >= 64 and O % 16 == 0 and _operand_units(B, po, C, 4) and (B * po >= 32768 or lim == 0))
+        wgrad = "fused" if fused and fwd != "library" else "library"
+    dgrad, wgrad = dgrad if needs.x else None, wgrad if needs.weight else None
+    split = 0
+    if wgrad == "fused":
+        tiles = 9 * (C // (128 if C % 128 == 0 else 64)) * -(-O // (128 if (O % 128 == 0 or O > 192) else 64))
+        split = max(1, min((B * po + 31) // 32, SphereConv2D.wgrad_workgroups // tiles, (512 << 20) // (O * 9 * C * 4)))
+    # the library weight gradient needs A9 again: kept (9x the input) where the forward made it, else rebuilt from x
+    return _ConvPlan(fwd, dgrad, wgrad, fwd == "library" and wgrad == "library", split)
+
+
 class _SphereConvFn(torch.autograd.Function):
     """``conv2d(grid_sample(x, grid), weight, bias, stride=3)`` (``sphere_cnn.py:121-124``).
 
-    Large layers (by the size of the would-be im2col operand ``A9``, thresholds in ``forward``; channel counts that
+    Large layers (by the size of the would-be im2col operand ``A9``, thresholds in ``_conv_plan``; channel counts that
     tile): the FUSED kernels of ``csrc/sphere_conv_fused.hip`` -- taps gathered straight into the LDS operand of an
     f32-MFMA implicit GEMM: forward (with the consumer's residual sum / activation in the epilogue), weight gradient, and
     the input gradient by the forward kernel on the transposed tap table, so the 9x blown-up operand never exists in HBM.
@@ -274,15 +339,6 @@ class _SphereConvFn(torch.autograd.Function):
         xr = x.permute(0, 2, 3, 1).contiguous()                   # (B,H,W,C); a view when x is channels-last
         O = weight.shape[0]
         w2 = _frozen_layout(weight, "w2", kind == "planar")       # columns ordered (tap, c) like A9
-        # which layers take the fused kernels: measured per shape (tools/sphere_layers.py, profiles/r02_sphere_layers.jsonl).
-        # They run at 85-115 TF/s; im2col + the library GEMM is faster only where the GEMM is wide (O >= 512) and the
-        # operand small -- there the library's 115-125 TF/s wins and A9 costs little memory.
-        a9_bytes = B * po * 9 * C * 4
-        lim = SphereConv2D.fused_min_bytes
-        ctx.fused_fwd = (B > 0 and C % 32 == 0 and O % 64 == 0 and
-                         (a9_bytes >= 32 * lim or (O <= 256 and a9_bytes >= lim)))
-        ctx.fused_dgrad, ctx.fused_wgrad = _backward_dispatch(B, po, C, O, stride)
-        a9 = None
         slope = float(slope)
         res = None
         if residual is not None:
@@ -290,50 +346,38 @@ class _SphereConvFn(torch.autograd.Function):
                 raise ValueError("SphereConv2D residual %s does not match the output (%d, %d, %d, %d)"
                                  % (tuple(residual.shape), B, O, geo.ho, geo.wo))
             res = residual.permute(0, 2, 3, 1).contiguous().view(B * po, O)    # a view when it is channels-last
-        # 3-channel input layers (SPADE's mlp_shared 3 -> 128, VGG's 3 -> 64; not the discriminator's 6 -> 64): bound by the
-        # write of their output -- one pass each way with the activation (and its backward, and the bias gradient) folded in
-        ctx.small = bool(B > 0 and res is None and L.eml_sphere_conv_small_supported(C, O))
-        # few-channel OUTPUT layers (conv_img 64 -> 3, the discriminators' final convolutions): one-pass kernels, no 9x operand
-        ctx.narrow = bool(SphereConv2D.narrow_kernels and B > 0 and res is None and slope == 1.0 and geo.idx1 is None
-                          and not ctx.small and L.eml_sphere_conv_narrow_supported(C, O))
-        # round 6: the low-resolution, wide layers (everything that used to fall through to im2col + a library GEMM below) on
-        # the footprint gather-GEMM of csrc/gather_gemm3.h; "force": wherever it is supported (tests, A/B), "off": round 5
-        mode = SphereConv2D.lowres
-        plan = None
-        if mode != "off" and kind == "sphere" and stride == 1 and not ctx.small and not ctx.narrow and (mode == "force" or not ctx.fused_fwd):
-            plan = _lowres_plan(geo, B, C, O)
-        ctx.lowres_dgrad = None
-        if mode != "off" and kind == "sphere" and stride == 1 and not ctx.small and not ctx.narrow and (mode == "force" or not ctx.fused_dgrad):
-            ctx.lowres_dgrad = _lowres_plan(geo, B, O, C, transposed=True) if ctx.needs_input_grad[0] else None
-        if ctx.narrow:
-            ctx.fused_fwd = ctx.fused_wgrad = ctx.fused_dgrad = False
-            y = torch.empty(B * po, O, dtype=torch.float32, device=x.device)
-            if SphereConv2D.narrow_project:   # round 6: project onto the 9 x O columns per SOURCE pixel, then gather 16 bytes per corner
-                scratch = torch.empty(L.eml_sphere_conv_narrow_scratch_floats(B, H * W), dtype=torch.float32, device=x.device)
-                _lib.check(L.eml_sphere_conv_narrow_fwd2_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2.contiguous()),
-                                                             p(bias.contiguous()) if bias is not None else None, p(y), p(scratch),
-                                                             B, H * W, po, C, O, st), "eml_sphere_conv_narrow_fwd2_f32")
-                del scratch
-            else:
-                _lib.check(L.eml_sphere_conv_narrow_fwd_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2.contiguous()),
-                                                            p(bias.contiguous()) if bias is not None else None, p(y), B, H * W, po,
-                                                            C, O, st), "eml_sphere_conv_narrow_fwd_f32")
-        elif ctx.small:
-            ctx.fused_fwd = ctx.fused_wgrad = False
-            y = torch.empty(B * po, O, dtype=torch.float32, device=x.device)
-            _lib.check(L.eml_sphere_conv_small_fwd_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2.contiguous()),
-                                                       p(bias.contiguous()) if bias is not None else None, p(y), B, H * W,
-                                                       po, C, O, slope, st), "eml_sphere_conv_small_fwd_f32")
-        elif plan is not None:
-            y = _lowres_conv(xr, geo.idx, geo.wgt, None, 4, plan, w2.contiguous(), bias.contiguous() if bias is not None else None,
-                             res, slope, B, H * W, po, C, O)
-        elif ctx.fused_fwd:
-            y = torch.empty(B * po, O, dtype=torch.float32, device=x.device)
+        nig = ctx.needs_input_grad    # (as many entries as ``apply`` got arguments)
+        needs = _Needs(nig[0], nig[1], nig[2], res is not None and nig[5])
+        # the footprint gather-GEMM of csrc/gather_gemm3.h (measured, not adopted): only when forced, wherever it supports the shape
+        low = low_t = None
+        if SphereConv2D.lowres == "force" and kind == "sphere" and stride == 1:
+            low = _lowres_plan(geo, B, C, O)
+            low_t = _lowres_plan(geo, B, O, C, transposed=True) if needs.x else None
+        plan = _conv_plan(kind, stride, B, C, O, H, W, res is not None, slope, needs,
+                          bool(L.eml_sphere_conv_small_supported(C, O)), bool(L.eml_sphere_conv_narrow_supported(C, O)),
+                          lowres=(low is not None, low_t is not None))
+        a9 = None
+        bc = bias.contiguous() if bias is not None else None
+        if plan.fwd not in ("lowres", "library"):
+            y, w2c = torch.empty(B * po, O, dtype=torch.float32, device=x.device), w2.contiguous()
+        if plan.fwd == "narrow" and SphereConv2D.narrow_project:
+            # project onto the 9 x O columns per SOURCE pixel, then gather 16 bytes per corner (csrc/sphere_conv_narrow2.hip)
+            scratch = torch.empty(L.eml_sphere_conv_narrow_scratch_floats(B, H * W), dtype=torch.float32, device=x.device)
+            _lib.check(L.eml_sphere_conv_narrow_fwd2_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2c), p(bc), p(y), p(scratch),
+                                                         B, H * W, po, C, O, st), "eml_sphere_conv_narrow_fwd2_f32")
+            del scratch
+        elif plan.fwd == "narrow":
+            _lib.check(L.eml_sphere_conv_narrow_fwd_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2c), p(bc), p(y), B, H * W, po, C, O, st),
+                       "eml_sphere_conv_narrow_fwd_f32")
+        elif plan.fwd == "small":
+            _lib.check(L.eml_sphere_conv_small_fwd_f32(p(xr), p(geo.idx), p(geo.wgt), p(w2c), p(bc), p(y), B, H * W, po, C, O, slope,
+                                                       st), "eml_sphere_conv_small_fwd_f32")
+        elif plan.fwd == "lowres":
+            y = _lowres_conv(xr, geo.wgt, None, 4, low, w2.contiguous(), bc, res, slope, B, H * W, po, C, O)
+        elif plan.fwd == "fused":
             tab = (geo.idx1, geo.wgt1, 1) if geo.idx1 is not None else (geo.idx, geo.wgt, 4)
-            _lib.check(L.eml_sphere_conv_fwd_fused_ex_f32(p(xr), p(tab[0]), p(tab[1]), p(w2.contiguous()),
-                                                          p(bias.contiguous()) if bias is not None else None, p(y), B,
-                                                          H * W, po, C, O, tab[2], p(res) if res is not None else None,
-                                                          slope, geo.rowshare if tab[2] == 4 else 0, st),
+            _lib.check(L.eml_sphere_conv_fwd_fused_ex_f32(p(xr), p(tab[0]), p(tab[1]), p(w2c), p(bc), p(y), B, H * W, po, C, O,
+                                                          tab[2], p(res), slope, geo.rowshare if tab[2] == 4 else 0, st),
                        "eml_sphere_conv_fwd_fused_ex_f32")
         else:
             a9 = _SphereConvFn._im2col(xr, geo, B, C) if B else xr.new_empty(0, 9 * C)
@@ -342,85 +386,64 @@ class _SphereConvFn(torch.autograd.Function):
                 y += res
             if slope != 1.0:
                 y = torch.relu_(y) if slope == 0.0 else nn.functional.leaky_relu_(y, slope)
-        # A9 exists (the forward ran as im2col + library GEMM: wide heads, O >= 512): the weight gradient is then ONE long-K
-        # library GEMM on it -- 145-152 TF/s on the recorded selection (_gemm_selection.py) against the fused kernel's 110,
-        # with no gather pass of its own.  (Round 5; before the GEMMs were tuned the fused kernel won above 256 MB of operand.)
-        if a9 is not None and SphereConv2D.lib_wgrad_on_kept_operand and SphereConv2D.keep_operand and weight.requires_grad:
-            ctx.fused_wgrad = False
-        # the library weight gradient needs A9 again: keep it (9x the input) or rebuild it from x; the fused one never does
-        ctx.keep = (a9 is not None and not ctx.fused_wgrad and SphereConv2D.keep_operand and weight.requires_grad)
-        ctx.slope = slope
         # an activation's derivative is taken from the OUTPUT's sign (valid for slope >= 0; the entry point rejects others)
-        ctx.save_for_backward(a9 if ctx.keep else xr, weight, *((y,) if slope != 1.0 else ()))
-        ctx.geo, ctx.has_bias, ctx.shape = geo, bias is not None, (B, C, H, W, O)
+        ctx.save_for_backward(a9 if plan.keep else xr, weight, *((y,) if slope != 1.0 else ()))
+        ctx.plan, ctx.needs, ctx.geo, ctx.shape = plan, needs, geo, (B, C, H, W, O)
+        ctx.has_bias, ctx.slope = bias is not None, slope
         return y.view(B, geo.ho, geo.wo, O).permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
-        return _sphere_conv_backward(ctx, gy, ctx.saved_tensors, ctx.needs_input_grad)
+        gx, gw, gb, gres = _sphere_conv_backward(ctx.plan, ctx.geo, ctx.shape, ctx.needs, gy, ctx.saved_tensors, ctx.has_bias,
+                                                 ctx.slope)
+        return gx, gw, gb, None, None, gres, None
 
 
-def _backward_dispatch(B, po, C, O, stride):
-    """(fused input gradient?, fused weight gradient?) of a SphereConv layer, measured per shape (tools/sphere_layers.py)."""
-    lim = SphereConv2D.fused_min_bytes
-    a9_bytes = B * po * 9 * C * 4
-    # input gradient: the forward kernel on the transposed tap table (K = 9*O, N = C).  Measured: it beats
-    # dY W2 (library) + col2im where the pixel count is large and O <= 256; wide heads (K = 9*O >= 4608) stay unfused
-    fused_dgrad = (B > 0 and O % 32 == 0 and C % 64 == 0 and stride == 1 and
-                   (lim == 0 or (O <= 256 and B * po >= 131072)))
-    # weight gradient: K = pixels; below ~32k pixels the split-K tiles are short and the library's long-K GEMM wins
-    fused_wgrad = (B > 0 and C % 64 == 0 and O >= 64 and O % 16 == 0 and a9_bytes >= 4 * lim and
-                   (B * po >= 32768 or lim == 0))
-    return fused_dgrad, fused_wgrad
-
-
-def _sphere_conv_backward(ctx, gy, saved, needs):
-    """Backward of ``_SphereConvFn`` given its recorded state ``ctx`` (geo, shape, slope, dispatch flags), the saved tensors and
-    the needs-gradient flags in ``forward``'s argument order; shared with the fused SPADE forward, whose backward feeds it the
-    (dgamma | dbeta) tensor."""
+def _sphere_conv_backward(plan, geo, shape, needs, gy, saved, has_bias, slope=1.0):
+    """Backward of a SphereConv layer that ran under ``plan`` (``_conv_plan``) -> (dx, dweight, dbias, dresidual).  ``shape``:
+    (B, C, H, W, O); ``needs``: a ``_Needs``; ``saved``: (the im2col operand where ``plan.keep`` else the pixel-major input, the
+    weight[, the output where slope != 1]).  Shared with the one-launch SPADE, whose backward feeds it the (dgamma | dbeta)
+    tensor."""
     from .. import _lib
     L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
     xr, weight = saved[:2]
-    geo = ctx.geo
-    B, C, H, W, O = ctx.shape
+    B, C, H, W, O = shape
     po = geo.ho * geo.wo
     gyr = gy.permute(0, 2, 3, 1).reshape(B * po, O).contiguous()
-    y = saved[2] if ctx.slope != 1.0 else None
+    y = saved[2] if slope != 1.0 else None
     gx = gw = gb = gres = None
+
+    def new(*size):
+        return torch.empty(*size, dtype=torch.float32, device=gy.device)
     # the 3-channel input layers: dW2, the bias gradient and the activation's backward in one pass over (dY, Y); where the
     # input itself carries a gradient (the guide map of the joint step, VGG's conv1_1 on the generated panorama) the masked
     # dY times W2 in one more pass (eml_sphere_conv_small_da9_f32) -- no activation-backward pass, no N = 27 library GEMM
-    small_w = ctx.small and needs[1]
-    small_x = ctx.small and needs[0] and B > 0 and SphereConv2D.small_input_grad
-    if ctx.small and needs[0] and not small_x:
-        small_w = False   # EML_SMALL_DA9=0 (A/B): round 4's dispatch -- the general path forms the masked dY once for both
+    small_w, small_x = plan.wgrad == "small", plan.dgrad == "small"
     if small_w:
-        part = torch.empty(L.eml_sphere_conv_small_wgrad_partial_floats(B, po, C, O), dtype=torch.float32, device=gy.device)
-        gw2 = torch.empty(O, 9 * C, dtype=torch.float32, device=gy.device)
-        gb_ = torch.empty(O, dtype=torch.float32, device=gy.device) if ctx.has_bias else None
-        _lib.check(L.eml_sphere_conv_small_wgrad_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(y) if y is not None else None,
-                                                     ctx.slope, p(part), p(gw2), p(gb_) if gb_ is not None else None, B,
+        part = new(L.eml_sphere_conv_small_wgrad_partial_floats(B, po, C, O))
+        gw2 = new(O, 9 * C)
+        gb_ = new(O) if has_bias else None
+        _lib.check(L.eml_sphere_conv_small_wgrad_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(y), slope, p(part), p(gw2), p(gb_), B,
                                                      H * W, po, C, O, st), "eml_sphere_conv_small_wgrad_f32")
-        gw = gw2.view(O, 3, 3, C).permute(0, 3, 1, 2)
-        gb = gb_ if (ctx.has_bias and needs[2]) else None
+        gw = _w2_as_weight(gw2, C)
+        gb = gb_ if needs.bias else None
         del part
     if small_x:
-        w2 = weight.permute(0, 2, 3, 1).reshape(O, 9 * C).contiguous()
-        da9 = torch.empty(B * po, 9 * C, dtype=torch.float32, device=gy.device)
-        _lib.check(L.eml_sphere_conv_small_da9_f32(p(gyr), p(y) if y is not None else None, ctx.slope, p(w2), p(da9), B * po, C, O,
-                                                   st), "eml_sphere_conv_small_da9_f32")
-        gxr = torch.empty(B, H, W, C, dtype=torch.float32, device=gy.device)
+        w2, da9 = _w2_of(weight).contiguous(), new(B * po, 9 * C)
+        _lib.check(L.eml_sphere_conv_small_da9_f32(p(gyr), p(y), slope, p(w2), p(da9), B * po, C, O, st),
+                   "eml_sphere_conv_small_da9_f32")
+        gxr = new(B, H, W, C)
         _lib.check(L.eml_sphere_col2im_f32(p(da9), p(geo.csr_ptr), p(geo.csr_src), p(geo.csr_w), p(gxr), B, H * W, po, C, st),
                    "eml_sphere_col2im_f32")
         gx = gxr.permute(0, 3, 1, 2)
-    need_masked = ((needs[0] and not small_x) or (len(needs) > 5 and needs[5])
-                   or (not small_w and (needs[1] or (ctx.has_bias and needs[2]))))
+    need_masked = ((needs.x and not small_x) or needs.residual
+                   or (not small_w and (needs.weight or (has_bias and needs.bias))))
     if y is not None and need_masked:
-        gyr = (torch.ops.aten.threshold_backward(gyr, y, 0.0) if ctx.slope == 0.0
-               else torch.ops.aten.leaky_relu_backward(gyr, y, ctx.slope, True))
-    if len(needs) > 5 and needs[5]:
+        gyr = (torch.ops.aten.threshold_backward(gyr, y, 0.0) if slope == 0.0
+               else torch.ops.aten.leaky_relu_backward(gyr, y, slope, True))
+    if needs.residual:
         gres = gyr.view(B, geo.ho, geo.wo, O).permute(0, 3, 1, 2)
-    if ctx.has_bias and needs[2] and not small_w:
+    if has_bias and needs.bias and not small_w:
         # the SPADE modulation's backward leaves the column sums of the dgb it produced on the tensor (f64-accumulated)
         # -- valid only for the very tensor it was computed from: same storage, not written since (autograd accumulates
         # IN PLACE into a gradient that has a second consumer; a hook may hand over a different tensor): ADVICE round 3
@@ -433,7 +456,7 @@ def _sphere_conv_backward(ctx, gy, saved, needs):
             gb = pre
         elif O <= 8 and gyr.is_cuda and B > 0:   # tall and skinny: ATen's sum(0) runs it on a few workgroups
             part = torch.empty(L.eml_colsum_partial_doubles(O), dtype=torch.float64, device=gy.device)
-            gb = torch.empty(O, dtype=torch.float32, device=gy.device)
+            gb = new(O)
             _lib.check(L.eml_colsum_f32(p(gyr), B * po, O, p(part), p(gb), st), "eml_colsum_f32")
         else:
             gb = gyr.sum(0)
@@ -441,84 +464,74 @@ def _sphere_conv_backward(ctx, gy, saved, needs):
             # the residual branch's gradient IS this (masked) dY: a learned shortcut's bias gradient (conv_s, architecture.py:60)
             # is the same column sum -- handed over on the tensor, under the same storage / version check as above
             gres._eml_colsum = (gb, gres.data_ptr(), gres._version)
-    narrow = getattr(ctx, "narrow", False)
+    # what only the tap table knows: a tiny geometry whose (pixel, tap) has more than 8 sources has no transposed table -- the
+    # kernels that gather through it then give way to the one-pass weight gradient / to dY W2 + col2im
+    via_tt = plan.dgrad in ("narrow", "fused") or (plan.wgrad == "narrow" and SphereConv2D.narrow_project)
+    tt = geo.transposed_table() if via_tt else None
     narrow_v = None   # the few-output-channel layers' V (B*HW, 36), left by the weight gradient for the input gradient
-    if needs[1] and not small_w:
-        ttn = geo.transposed_table() if (narrow and SphereConv2D.narrow_project and B) else None
-        if narrow and ttn is not None:
-            # round 6: what every output pixel sends back to a source pixel through each tap (the transposed table), (B*HW, 36),
-            # then a 36 x C product over the pixels -- nothing is gathered at full channel width
-            tidx, twgt, rowmax, ke = ttn
-            scratch = torch.empty(L.eml_sphere_conv_narrow_scratch_floats(B, H * W), dtype=torch.float32, device=gy.device)
-            part = torch.empty(L.eml_sphere_conv_narrow_wgrad2_partial_floats(B, H * W, C), dtype=torch.float32, device=gy.device)
-            gw2 = torch.empty(O, 9 * C, dtype=torch.float32, device=gy.device)
-            _lib.check(L.eml_sphere_conv_narrow_wgrad2_f32(p(xr), p(tidx), p(twgt), ke, p(rowmax) if ke == 8 else None, p(gyr),
-                                                           p(scratch), p(part), p(gw2), B, H * W, po, C, O, st),
-                       "eml_sphere_conv_narrow_wgrad2_f32")
-            gw = gw2.view(O, 3, 3, C).permute(0, 3, 1, 2)
-            del part
-            narrow_v = scratch     # V stays for the input gradient below
-        elif narrow:
-            part = torch.empty(L.eml_sphere_conv_narrow_wgrad_partial_floats(B, po, C, O), dtype=torch.float32, device=gy.device)
-            gw2 = torch.empty(O, 9 * C, dtype=torch.float32, device=gy.device)
-            _lib.check(L.eml_sphere_conv_narrow_wgrad_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(part), p(gw2), B, H * W, po, C,
-                                                          O, st), "eml_sphere_conv_narrow_wgrad_f32")
-            gw = gw2.view(O, 3, 3, C).permute(0, 3, 1, 2)
-            del part
-        elif ctx.fused_wgrad and B:
-            bn = 128 if C % 128 == 0 else 64
-            bmo = 128 if (O % 128 == 0 or O > 192) else 64
-            tiles = 9 * (C // bn) * ((O + bmo - 1) // bmo)
-            nchunks = (B * po + 31) // 32
-            split = max(1, min(nchunks, SphereConv2D.wgrad_workgroups // tiles, (512 << 20) // (O * 9 * C * 4)))
-            part = torch.empty(L.eml_sphere_conv_wgrad_partial_floats(C, O, split), dtype=torch.float32, device=gy.device)
-            gw2 = torch.empty(O, 9 * C, dtype=torch.float32, device=gy.device)
-            _lib.check(L.eml_sphere_conv_wgrad_fused_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(part), p(gw2), B,
-                                                         H * W, po, C, O, split, st), "eml_sphere_conv_wgrad_fused_f32")
-            gw = gw2.view(O, 3, 3, C).permute(0, 3, 1, 2)
-            del part
+    if plan.wgrad == "narrow" and tt is not None and SphereConv2D.narrow_project:
+        # what every output pixel sends back to a source pixel through each tap (the transposed table), (B*HW, 36), then a
+        # 36 x C product over the pixels -- nothing is gathered at full channel width (csrc/sphere_conv_narrow2.hip)
+        tidx, twgt, rowmax, ke = tt
+        narrow_v = new(L.eml_sphere_conv_narrow_scratch_floats(B, H * W))     # V stays for the input gradient below
+        part = new(L.eml_sphere_conv_narrow_wgrad2_partial_floats(B, H * W, C))
+        gw2 = new(O, 9 * C)
+        _lib.check(L.eml_sphere_conv_narrow_wgrad2_f32(p(xr), p(tidx), p(twgt), ke, p(rowmax) if ke == 8 else None, p(gyr),
+                                                       p(narrow_v), p(part), p(gw2), B, H * W, po, C, O, st),
+                   "eml_sphere_conv_narrow_wgrad2_f32")
+        gw = _w2_as_weight(gw2, C)
+        del part
+    elif plan.wgrad == "narrow":
+        part = new(L.eml_sphere_conv_narrow_wgrad_partial_floats(B, po, C, O))
+        gw2 = new(O, 9 * C)
+        _lib.check(L.eml_sphere_conv_narrow_wgrad_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(part), p(gw2), B, H * W, po, C,
+                                                      O, st), "eml_sphere_conv_narrow_wgrad_f32")
+        gw = _w2_as_weight(gw2, C)
+        del part
+    elif plan.wgrad == "fused":
+        part = new(L.eml_sphere_conv_wgrad_partial_floats(C, O, plan.split))
+        gw2 = new(O, 9 * C)
+        _lib.check(L.eml_sphere_conv_wgrad_fused_f32(p(xr), p(geo.idx), p(geo.wgt), p(gyr), p(part), p(gw2), B,
+                                                     H * W, po, C, O, plan.split, st), "eml_sphere_conv_wgrad_fused_f32")
+        gw = _w2_as_weight(gw2, C)
+        del part
+    elif plan.wgrad == "library":
+        a9 = xr if plan.keep else _SphereConvFn._im2col(xr, geo, B, C)
+        m_rows, split = B * po, 1
+        if (9 * C <= 64 or O <= 16) and m_rows >= 65536:
+            # skinny product (the 3- / 6-channel input layers: 27 or 54 columns against ~1 M rows; the 3-channel output layers:
+            # 1.9 TF/s as one GEMM): as ONE GEMM the library runs it on a handful of workgroups (1.6 ms for 7 GFLOP); as a
+            # batched split-K it is the HBM-bound read of dY it should be, followed by a fixed-order sum of the partials
+            split = 512
+            while m_rows % split:
+                split //= 2
+        if split > 1:
+            gw2 = torch.bmm(a9.view(split, m_rows // split, 9 * C).transpose(1, 2),
+                            gyr.view(split, m_rows // split, O)).sum(0)
         else:
-            a9 = xr if ctx.keep else _SphereConvFn._im2col(xr, geo, B, C)
-            m_rows, split = B * po, 1
-            if (9 * C <= 64 or O <= 16) and m_rows >= 65536:
-                # skinny product (the 3- / 6-channel input layers: 27 or 54 columns against ~1 M rows; the 3-channel
-                # output layers: 1.9 TF/s as one GEMM): as ONE GEMM
-                # the library runs it on a handful of workgroups (1.6 ms for 7 GFLOP); as a batched split-K it is
-                # the HBM-bound read of dY it should be, followed by a fixed-order sum of the partials
-                split = 512
-                while m_rows % split:
-                    split //= 2
-            if split > 1:
-                gw2 = torch.bmm(a9.view(split, m_rows // split, 9 * C).transpose(1, 2),
-                                gyr.view(split, m_rows // split, O)).sum(0)
-                gw = gw2.t().contiguous().view(O, 3, 3, C).permute(0, 3, 1, 2)
-            else:
-                # (9C, O) = A9^T gy, then one transposing copy into the (O, tap, c) layout of every other weight gradient.
-                # (gy^T A9 gives that layout directly: measured in round 5 on the recorded GEMM selection -- the copies it saves,
-                # 0.5 ms per joint step, are what that orientation's GEMMs lose: profiles/r05_ab_dispatch_late.txt)
-                gw2 = a9.t() @ gyr
-                gw = gw2.t().contiguous().view(O, 3, 3, C).permute(0, 3, 1, 2)
-            del a9
-    if needs[0] and not small_x:
-        lowres = getattr(ctx, "lowres_dgrad", None)
-        gxr = torch.empty(B, H, W, C, dtype=torch.float32, device=gy.device) if (lowres is None or narrow or not B) else None
-        tt = geo.transposed_table() if ((ctx.fused_dgrad or narrow or lowres is not None) and B) else None
-        if tt is not None and lowres is not None and not narrow:
-            # the footprint gather-GEMM over the transposed table (round 6): dY's rows of the few source rows in LDS
-            tidx, twgt, rowmax, ke = tt
+            # (9C, O) = A9^T gy, then one transposing copy into the (O, tap, c) layout of every other weight gradient.
+            # (gy^T A9 gives that layout directly: measured in round 5 on the recorded GEMM selection -- the copies it saves,
+            # 0.5 ms per joint step, are what that orientation's GEMMs lose: profiles/r05_ab_dispatch_late.txt)
+            gw2 = a9.t() @ gyr
+        gw = _w2_as_weight(gw2.t().contiguous(), C)
+        del a9
+    if plan.dgrad is not None and not small_x:
+        low_t = _lowres_plan(geo, B, O, C, transposed=True) if plan.dgrad == "lowres" else None
+        if low_t is not None:
+            # the footprint gather-GEMM over the transposed table: dY's rows of the few source rows in LDS
+            tidx, twgt, rowmax, ke = geo.transposed_table()
             w2t = weight.permute(1, 2, 3, 0).reshape(C, 9 * O).contiguous()   # columns ordered (tap, o)
-            gxr = _lowres_conv(gyr, tidx, twgt, rowmax if ke == 8 else None, ke, lowres, w2t, None, None, 1.0, B, po, H * W, O,
+            gxr = _lowres_conv(gyr, twgt, rowmax if ke == 8 else None, ke, low_t, w2t, None, None, 1.0, B, po, H * W, O,
                                C).view(B, H, W, C)
-        elif tt is not None and narrow:
+        elif plan.dgrad == "narrow" and tt is not None:
             tidx, twgt, rowmax, ke = tt
-            w2 = weight.permute(0, 2, 3, 1).reshape(O, 9 * C).contiguous()
-            # round 6: dX = V W2 on the matrix unit, V shared with the weight gradient -- for conv_img's width (372 -> 86 us); the
+            gxr, w2 = new(B, H, W, C), _w2_of(weight).contiguous()
+            # dX = V W2 on the matrix unit, V shared with the weight gradient -- for conv_img's width (372 -> 86 us); the
             # discriminators' 512-channel heads keep the one-pass kernel (a workgroup would stage 74 KB of weights for a few
             # thousand pixels: 35 -> 31 us at 15 x 31, 12 -> 20 us at 7 x 15; tools/bench_narrow.py)
             if SphereConv2D.narrow_project and C <= 128:
                 has_v = narrow_v is not None
-                scratch = narrow_v if has_v else torch.empty(L.eml_sphere_conv_narrow_scratch_floats(B, H * W), dtype=torch.float32,
-                                                             device=gy.device)
+                scratch = narrow_v if has_v else new(L.eml_sphere_conv_narrow_scratch_floats(B, H * W))
                 _lib.check(L.eml_sphere_conv_narrow_dgrad2_f32(p(gyr), p(tidx), p(twgt), ke, p(rowmax) if ke == 8 else None, p(w2),
                                                                p(gxr), p(scratch), int(has_v), B, H * W, po, C, O, st),
                            "eml_sphere_conv_narrow_dgrad2_f32")
@@ -526,16 +539,17 @@ def _sphere_conv_backward(ctx, gy, saved, needs):
             else:
                 _lib.check(L.eml_sphere_conv_narrow_dgrad_f32(p(gyr), p(tidx), p(twgt), ke, p(w2), p(gxr), B, H * W, po, C, O, st),
                            "eml_sphere_conv_narrow_dgrad_f32")
-        elif tt is not None:
+        elif plan.dgrad == "fused" and tt is not None:
             # gather-GEMM over the transposed tap table: neither dA9 (B*Po, 9C) nor its col2im pass exist
             tidx, twgt, rowmax, ke = tt
+            gxr = new(B, H, W, C)
             w2t = _frozen_layout(weight, "w2t", geo.idx1 is not None)          # columns ordered (tap, o)
             _lib.check(L.eml_sphere_conv_dgrad_fused_f32(p(gyr), p(tidx), p(twgt), p(rowmax), ke, p(w2t), p(gxr), B,
                                                          H * W, po, C, O, getattr(geo, "t_rowshare", 0), st),
                        "eml_sphere_conv_dgrad_fused_f32")
         else:
-            w2 = weight.permute(0, 2, 3, 1).reshape(O, 9 * C)
-            da9 = gyr @ w2                                           # (B*Po, 9C)
+            gxr = new(B, H, W, C)
+            da9 = gyr @ _w2_of(weight)                                   # (B*Po, 9C)
             if B:
                 _lib.check(L.eml_sphere_col2im_f32(p(da9), p(geo.csr_ptr), p(geo.csr_src), p(geo.csr_w), p(gxr), B,
                                                    H * W, po, C, st), "eml_sphere_col2im_f32")
@@ -549,7 +563,7 @@ def _sphere_conv_backward(ctx, gy, saved, needs):
         if slot is not None and slot.shape == gw.shape and slot.device == gw.device:
             slot.copy_(gw)
             gw = slot
-    return gx, gw, gb, None, None, gres, None
+    return gx, gw, gb, gres
 
 
 def sphere_conv(x, weight, bias, stride=1, residual=None, act_slope=1.0):
@@ -571,7 +585,7 @@ def _frozen_layout(weight, kind, remember=False):
     forward passes and one input-gradient pass per iteration, up to 9.4 MB each -- is copied once per (object, version, storage);
     a frozen weight rewritten through ``.data`` in place is not seen (no version bump): write it under ``torch.no_grad()``."""
     O, C = weight.shape[0], weight.shape[1]
-    view = (weight.permute(0, 2, 3, 1).reshape(O, 9 * C) if kind == "w2" else weight.permute(1, 2, 3, 0).reshape(C, 9 * O))
+    view = _w2_of(weight) if kind == "w2" else weight.permute(1, 2, 3, 0).reshape(C, 9 * O)
     # only a Parameter object that takes no gradient is remembered, and only while it is THAT object at THAT version (a
     # computed weight -- spectral norm under no_grad -- is a new tensor every call whose address the allocator reuses)
     # ... and only for the planar convolutions (``remember``: the VGG19 stack, which no optimizer holds).  A discriminator frozen
@@ -749,31 +763,45 @@ class _SpadeNormModulateFn(torch.autograd.Function):
         dgb = torch.empty((B, 2 * C, H, W), dtype=torch.float32, device=x.device, memory_format=cl)
         dxn = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device, memory_format=cl)
         grid = _stats_grid(rows, C)
-        # one pass: dxn, dgb, BatchNorm's (sum dxn, sum dxn*xhat) and the column sums of dgb (= the bias gradient of the
-        # gamma | beta convolution, handed to its backward on the tensor itself instead of a second read of dgb)
+        # one pass: dxn, dgb, BatchNorm's (sum dxn, sum dxn*xhat) and the column sums of dgb
         partials = torch.empty(grid, 4 * C + 1, dtype=torch.float64, device=x.device)
         _lib.check(L.eml_spade_norm_modulate_bwd_cols_f32(p(gy), p(x), p(gb), p(dxn), p(dgb), B, H, W, C, int(ctx.up2), ctx.slope,
                                                           p(mean), p(istd), p(partials), grid, st),
                    "eml_spade_norm_modulate_bwd_cols_f32")
-        folded = torch.empty(4 * C + 1, dtype=torch.float64, device=x.device)
-        _lib.check(L.eml_bn_fold_f64(p(partials), grid, 4 * C + 1, p(folded), st), "eml_bn_fold_f64")
-        sums = None
-        if ctx.training:
-            sums = folded[:2 * C + 1]
-            sums[2 * C:].fill_(float(rows))
-            if _bn_sync():
-                import torch.distributed as dist
-                dist.all_reduce(sums)
-        dgb._eml_colsum = (folded[2 * C + 1:].view(C, 2).t().reshape(2 * C).float(), dgb.data_ptr(), dgb._version)
-        if ctx.up2:
-            dx = torch.empty_like(x, memory_format=cl)     # gradient of the map BEFORE the upsample
-            _lib.check(L.eml_bn_bwd_apply_up2_f32(p(dxn), p(x), B, H, W, C, p(mean), p(istd), p(sums), p(dx), st),
-                       "eml_bn_bwd_apply_up2_f32")
-        else:
-            dx = dxn
-            _lib.check(L.eml_bn_bwd_apply_f32(p(dx), C, p(x), C, rows, C, p(mean), p(istd), p(sums), p(dx), C, st),
-                       "eml_bn_bwd_apply_f32")
+        dx = _spade_bn_backward_tail(partials, x, dxn, dgb, mean, istd, (B, H, W, C), ctx.up2, ctx.training)
         return dx, dgb, None, None, None, None, None
+
+
+def _spade_bn_backward_tail(partials, x, dxn, dgb, mean, istd, shape, up2, training, need_dx=True):
+    """What both SPADE backwards do with the [grid][4C+1] f64 partials of their modulation pass: fold them; BatchNorm's sums
+    (training: with the row count, all-reduced across ranks) finish dx = istd*(dxn - S1/n - xhat*S2/n) in one streaming pass
+    (``need_dx``; -> dx, on the grid BEFORE the upsample for ``up2``); the column sums of dgb -- the bias gradient of the
+    gamma | beta convolution -- ride on the tensor to that convolution's backward instead of a second read of dgb."""
+    from .. import _lib
+    L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
+    B, H, W, C = shape
+    rows = B * H * W
+    folded = torch.empty(4 * C + 1, dtype=torch.float64, device=x.device)
+    _lib.check(L.eml_bn_fold_f64(p(partials), partials.shape[0], 4 * C + 1, p(folded), st), "eml_bn_fold_f64")
+    sums = None
+    if training:
+        sums = folded[:2 * C + 1]
+        sums[2 * C:].fill_(float(rows))
+        if _bn_sync():
+            import torch.distributed as dist
+            dist.all_reduce(sums)
+    dgb._eml_colsum = (folded[2 * C + 1:].view(C, 2).t().reshape(2 * C).float(), dgb.data_ptr(), dgb._version)
+    if not need_dx:
+        return None
+    if up2:
+        dx = torch.empty_like(x, memory_format=torch.channels_last)     # gradient of the map BEFORE the upsample
+        _lib.check(L.eml_bn_bwd_apply_up2_f32(p(dxn), p(x), B, H, W, C, p(mean), p(istd), p(sums), p(dx), st),
+                   "eml_bn_bwd_apply_up2_f32")
+    else:
+        dx = dxn
+        _lib.check(L.eml_bn_bwd_apply_f32(p(dx), C, p(x), C, rows, C, p(mean), p(istd), p(sums), p(dx), C, st),
+                   "eml_bn_bwd_apply_f32")
+    return dx
 
 
 _SPADE_ROWS = {}
@@ -816,7 +844,7 @@ class _SpadeHeadsFn(torch.autograd.Function):
         Cn, Cin = wg.shape[0], wg.shape[1]
         w2, b2 = spade_heads_w2(wg, wb, bg, bb, False)
         ctx.Cn, ctx.has_b = Cn, b2 is not None
-        w = w2.view(2 * Cn, 3, 3, Cin).permute(0, 3, 1, 2)
+        w = _w2_as_weight(w2, Cin)
         if b2 is None:
             b2 = w2.new_zeros(0)
             ctx.mark_non_differentiable(b2)
@@ -862,11 +890,14 @@ class _SpadeConvModulateFn(torch.autograd.Function):
                                                    p(x), p(mean), p(istd), p(y), p(gamma) if keep else None, B, H, W, Cin, Cn,
                                                    int(bool(up2)), float(slope), geo.rowshare, st), "eml_sphere_conv_spade_fwd_f32")
         ctx.geo, ctx.shape, ctx.has_bias = geo, (B, Cin, H, W, 2 * Cn), br is not None
-        ctx.up2, ctx.act_slope, ctx.training = bool(up2), float(slope), bool(training)
-        # the state _sphere_conv_backward reads: a plain (no epilogue, no kept operand) SphereConv 128 -> 2 Cn
-        ctx.slope, ctx.small, ctx.keep = 1.0, False, False
-        ctx.fused_dgrad, ctx.fused_wgrad = _backward_dispatch(B, H * W, Cin, 2 * Cn, 1)
+        ctx.up2, ctx.slope, ctx.training = bool(up2), float(slope), bool(training)
         if keep:
+            # the backward of the gamma | beta convolution: a plain (no epilogue) SphereConv Cin -> 2 Cn whose forward ran here
+            # and left no operand; neither a 3-channel-input nor a few-output-channel layer (eml_sphere_conv_spade_supported:
+            # Cin >= 64, Cn >= 64)
+            nig = ctx.needs_input_grad
+            ctx.needs = _Needs(nig[1], nig[2] or nig[3], br is not None and (nig[4] or nig[5]), False)
+            ctx.plan = _conv_plan("sphere", 1, B, Cin, 2 * Cn, H, W, False, 1.0, ctx.needs, False, False, fwd="fused")
             ctx.save_for_backward(ar, wg, wb, x, gamma, y, mean, istd)
         return y.view(B, H, W, Cn).permute(0, 3, 1, 2)
 
@@ -877,45 +908,20 @@ class _SpadeConvModulateFn(torch.autograd.Function):
         ar, wg, wb, x, gamma, y, mean, istd = ctx.saved_tensors
         B, Cin, H, W, O = ctx.shape
         C = O // 2
-        rows = B * H * W
         cl = torch.channels_last
         gy = gy.contiguous(memory_format=cl)
         dgb = torch.empty((B, 2 * C, H, W), dtype=torch.float32, device=x.device, memory_format=cl)
         dxn = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device, memory_format=cl)
-        grid = _stats_grid(rows, C)
+        grid = _stats_grid(B * H * W, C)
         partials = torch.empty(grid, 4 * C + 1, dtype=torch.float64, device=x.device)
         _lib.check(L.eml_spade_norm_modulate_bwd_y_f32(p(gy), p(x), p(gamma), p(y), p(dxn), p(dgb), B, H, W, C, int(ctx.up2),
-                                                       ctx.act_slope, p(mean), p(istd), p(partials), grid, st),
+                                                       ctx.slope, p(mean), p(istd), p(partials), grid, st),
                    "eml_spade_norm_modulate_bwd_y_f32")
-        folded = torch.empty(4 * C + 1, dtype=torch.float64, device=x.device)
-        _lib.check(L.eml_bn_fold_f64(p(partials), grid, 4 * C + 1, p(folded), st), "eml_bn_fold_f64")
-        sums = None
-        if ctx.training:
-            sums = folded[:2 * C + 1]
-            sums[2 * C:].fill_(float(rows))
-            if _bn_sync():
-                import torch.distributed as dist
-                dist.all_reduce(sums)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if ctx.up2:
-                dx = torch.empty_like(x, memory_format=cl)     # gradient of the map BEFORE the upsample
-                _lib.check(L.eml_bn_bwd_apply_up2_f32(p(dxn), p(x), B, H, W, C, p(mean), p(istd), p(sums), p(dx), st),
-                           "eml_bn_bwd_apply_up2_f32")
-            else:
-                dx = dxn
-                _lib.check(L.eml_bn_bwd_apply_f32(p(dx), C, p(x), C, rows, C, p(mean), p(istd), p(sums), p(dx), C, st),
-                           "eml_bn_bwd_apply_f32")
-        # the column sums of dgb = the bias gradient of the gamma | beta convolution (see _SpadeNormModulateFn.backward)
-        dgb._eml_colsum = (folded[2 * C + 1:].view(C, 2).t().reshape(2 * C).float(), dgb.data_ptr(), dgb._version)
         nig = ctx.needs_input_grad
-        need_w, need_b = nig[2] or nig[3], ctx.has_bias and (nig[4] or nig[5])
-        needs = (nig[1], need_w, need_b, False, False, False, False)
+        dx = _spade_bn_backward_tail(partials, x, dxn, dgb, mean, istd, (B, H, W, C), ctx.up2, ctx.training, need_dx=nig[0])
         # the input gradient wants the heads in cat order: the same one-launch re-layout, without the row reorder
-        wnat = None
-        if nig[1]:
-            wnat = spade_heads_w2(wg, wb, None, None, False)[0].view(O, 3, 3, Cin).permute(0, 3, 1, 2)
-        gactv, gw, gbias = _sphere_conv_backward(ctx, dgb, (ar, wnat), needs)[:3]
+        wnat = _w2_as_weight(spade_heads_w2(wg, wb, None, None, False)[0], Cin) if nig[1] else None
+        gactv, gw, gbias, _ = _sphere_conv_backward(ctx.plan, ctx.geo, ctx.shape, ctx.needs, dgb, (ar, wnat), ctx.has_bias)
         gwg = gw[:C] if (gw is not None and nig[2]) else None
         gwb = gw[C:] if (gw is not None and nig[3]) else None
         gbg = gbias[:C] if (gbias is not None and nig[4]) else None
@@ -944,12 +950,11 @@ def _spade_conv_fusable(x, actv, C, up2):
         return False
     if not _lib.lib().eml_sphere_conv_spade_supported(Cin, C, H * W):
         return False
-    lim = SphereConv2D.fused_min_bytes
-    a9_bytes = B * H * W * 9 * Cin * 4
+    big = lambda units: _operand_units(B, H * W, Cin, units)
     # (round 5, with the library GEMMs on their recorded selection: sending the 2C = 512 SPADEs down the two-launch path when a
     # backward follows -- so that their weight gradient becomes a library GEMM on the kept operand -- wins 0.36 ms per weight
     # gradient and loses 0.42 ms per forward, the one-launch kernel runs these at 133 TF/s: measured, not adopted)
-    return a9_bytes >= 32 * lim or (2 * C <= 256 and a9_bytes >= lim) or (2 * C <= 512 and a9_bytes >= 8 * lim)
+    return big(32) or (2 * C <= 256 and big(1)) or (2 * C <= 512 and big(8))
 
 
 def spade_norm_modulate(x, bn, actv, conv_gamma, conv_beta, slope=1.0, stats=None, up2=False):
@@ -1060,7 +1065,7 @@ class _FusedSpectralNormHook:
             if pre is not None and pre[0] != self.key(module, w, u, v):
                 pre = None
             w2 = _SpectralW2Fn.apply(w, u, v, module.training, sn.eps, None if pre is None else pre[1])
-            wn = w2.view(O, 3, 3, C).permute(0, 3, 1, 2)
+            wn = _w2_as_weight(w2, C)
             if not isinstance(module, SphereConv2D):
                 # an nn.Conv2d (the crop encoder's stride-2 layers) runs on MIOpen, which takes a channels-last WEIGHT down a
                 # path 20x slower than its NCHW one (measured: 25.4 against 1.1 ms per joint step, profiles/r05_ab_sn_conv2d.txt):
@@ -1192,27 +1197,20 @@ class SphereConv2D(nn.Module):
     reference (``sphere_cnn.py:87-109``).  Runs on the MI355X only (``sphere_conv`` above); the reference's two
     stock ops (grid_sample + conv2d) are restated in ``oracle/projector.py`` for the tests."""
 
-    keep_operand = True   # unfused layers: keep the im2col operand of a training forward for the weight gradient
-    # unit of the fused-kernel thresholds on the size of the im2col operand (see forward); EML_FUSED_MIN_MB: A/B knob
+    # unit of the fused-kernel thresholds on the size of the im2col operand (see _conv_plan); EML_FUSED_MIN_MB: A/B knob
     fused_min_bytes = knob_int("EML_FUSED_MIN_MB", 64, lo=0) << 20
     # SPADE's gamma | beta convolution with the modulation as its epilogue (_SpadeConvModulateFn); EML_FUSE_SPADE=0: A/B knob
     fuse_spade = knob_flag("EML_FUSE_SPADE", True)
-    # O <= 4 layers on the one-pass kernels of csrc/sphere_conv_narrow.hip; EML_NARROW=0: A/B knob (im2col + library GEMM)
-    narrow_kernels = knob_flag("EML_NARROW", True)
-    # round 6: those layers as project-then-gather (csrc/sphere_conv_narrow2.hip); EML_NARROW_PROJECT=0: the one-pass kernels (A/B)
+    # the O <= 4 layers as project-then-gather (csrc/sphere_conv_narrow2.hip); EML_NARROW_PROJECT=0: the one-pass kernels of
+    # csrc/sphere_conv_narrow.hip (A/B)
     narrow_project = knob_flag("EML_NARROW_PROJECT", True)
-    # low-resolution wide layers on the footprint gather-GEMM (csrc/gather_gemm3.h) instead of im2col + a library GEMM;
-    # EML_LOWRES: A/B knob -- off = round 5's dispatch, force = wherever the kernel supports the shape
-    lowres = knob_choice("EML_LOWRES", "off", ("auto", "off", "force"))
-    # input gradient of the 3-channel input layers through eml_sphere_conv_small_da9_f32; EML_SMALL_DA9=0: A/B knob (general path)
-    small_input_grad = knob_flag("EML_SMALL_DA9", True)
+    # "force": the footprint gather-GEMM (csrc/gather_gemm3.h; measured, not adopted: DESIGN 11.2) wherever it supports the
+    # shape -- set by its parity test and tools/bench_lowres.py
+    lowres = "off"
     # split-K of the fused weight gradient: workgroups per launch (tiles x K-splits).  Two resident workgroups per CU: 1024 is
     # two full waves of them; round 4's 2048 wrote and re-read twice the partial sums for nothing (same-box A/B of the joint
     # step: 2048 -> 1024 -1.6 ms, 4096 +3 ms; profiles/r05_ab_wgrad_split.txt).  EML_WGRAD_WGS: A/B knob
     wgrad_workgroups = knob_int("EML_WGRAD_WGS", 1024, lo=256)
-    # layers whose forward left the im2col operand behind take the library's long-K GEMM for the weight gradient;
-    # EML_WGRAD_LIB_KEPT=0: A/B knob (round 4's rule: fused above 256 MB of operand and 32 k pixels)
-    lib_wgrad_on_kept_operand = knob_flag("EML_WGRAD_LIB_KEPT", True)
 
     def __init__(self, in_c, out_c, stride=1, bias=True, mode="bilinear"):
         super().__init__()

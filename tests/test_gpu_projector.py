@@ -249,15 +249,30 @@ def test_ngf64_shape_list_is_what_the_networks_run(monkeypatch):
     assert seen == set(NGF64_SHAPES), (sorted(seen - set(NGF64_SHAPES)), sorted(set(NGF64_SHAPES) - seen))
 
 
+def _plan_entry_points(plan, Cin):
+    """The SphereConv entry points a forward + backward under ``plan`` calls, with every gradient wanted, on a geometry that has
+    a transposed tap table (all but the tiniest) and the default ``narrow_project``."""
+    fwd = {"narrow": "conv_narrow_fwd2", "small": "conv_small_fwd", "fused": "conv_fwd_fused_ex", "library": "im2col"}[plan.fwd]
+    dgrad = {"narrow": ["conv_narrow_dgrad2" if Cin <= 128 else "conv_narrow_dgrad"], "small": ["conv_small_da9", "col2im"],
+             "fused": ["conv_dgrad_fused"], "library": ["col2im"]}[plan.dgrad]
+    wgrad = {"narrow": "conv_narrow_wgrad2", "small": "conv_small_wgrad", "fused": "conv_wgrad_fused",
+             "library": "im2col"}[plan.wgrad]     # (the library weight gradient: on the kept operand, or on a rebuilt one)
+    assert plan.keep == (plan.fwd == "library" and plan.wgrad == "library")
+    return {"eml_sphere_%s_f32" % n for n in [fwd, wgrad] + dgrad}
+
+
 @pytest.mark.parametrize("B,Cin,Cout,H,W,stride", NGF64_SHAPES)
 def test_sphere_conv_ngf64_layer_shapes_natural_dispatch(B, Cin, Cout, H, W, stride, monkeypatch):
     """The projector at its REAL size never met the oracle layer by layer: the reference golden is ngf = 8, and the per-shape
-    dispatch rules (fused gather-GEMM kernels vs im2col + library GEMM, ``_SphereConvFn.forward``) pick different kernels
+    dispatch rules (fused gather-GEMM kernels vs im2col + library GEMM, ``spherenet._conv_plan``) pick different kernels
     at ngf = 64.  Every distinct layer geometry of NGF64_SHAPES, at BASELINE's batch, with the dispatch left alone:
     output, d/dx, d/dweight, d/dbias against grid_sample + conv2d(stride 3) (sphere_cnn.py:111-124) in torch f32.
     Bounds: f32 sums over K = 9*Cin (forward), 9*Cout (d/dx), B*H'*W' (d/dweight) terms in two different orders agree to
-    ~sqrt(K) * 6e-8 of the sum's scale -- 1e-4 relative + 1e-4 of the tensor's largest entry covers K up to 1e6."""
+    ~sqrt(K) * 6e-8 of the sum's scale -- 1e-4 relative + 1e-4 of the tensor's largest entry covers K up to 1e6.
+    The convolution's entry points that ran are exactly those of the layer's plan (``_conv_plan``, pinned per shape on the CPU by
+    tests/test_sphere_conv_plan.py)."""
     from emlight_amd import _lib
+    from emlight_amd.GenProjector import spherenet
     from emlight_amd.GenProjector.spherenet import SphereConv2D
     torch.manual_seed(Cin * 7 + Cout + H)
     hip = SphereConv2D(Cin, Cout, stride=stride, bias=True).cuda()
@@ -295,6 +310,12 @@ def test_sphere_conv_ngf64_layer_shapes_natural_dispatch(B, Cin, Cout, H, W, str
     yr = torch.cat(ys, 0)
     assert yh.shape == yr.shape == (B, Cout, H // stride, W // stride)
     print("dispatch", (B, Cin, Cout, H, W, stride), sorted(n.replace("eml_sphere_", "") for n in seen))
+    # the convolution's own entry points are exactly the ones the layer's plan names (tests/test_sphere_conv_plan.py pins the plan)
+    plan = spherenet._conv_plan("sphere", stride, B, Cin, Cout, H, W, False, 1.0, spherenet._Needs(True, True, True, False),
+                                bool(real.eml_sphere_conv_small_supported(Cin, Cout)),
+                                bool(real.eml_sphere_conv_narrow_supported(Cin, Cout)))
+    ran = {n for n in seen if n.startswith("eml_sphere_") and not n.endswith(("_supported", "_floats", "tap_table_f32"))}
+    assert ran == _plan_entry_points(plan, Cin), (plan, sorted(ran))
     for name, a, b in [("y", yh.detach(), yr.detach()), ("dx", xh.grad, xr.grad), ("dW", hip.weight.grad, wr.grad),
                        ("db", hip.bias.grad, br.grad)]:
         s_ = float(b.abs().max())

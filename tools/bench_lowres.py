@@ -1,5 +1,5 @@
 """Round 6: the low-resolution wide SphereConv layers of the ngf = 64 projector (B = 32 per GPU; the discriminators see 64) --
-the footprint gather-GEMM (csrc/gather_gemm3.h, EML_LOWRES=force) against round 5's dispatch (EML_LOWRES=off: gather_gemm2 or
+the footprint gather-GEMM (csrc/gather_gemm3.h, SphereConv2D.lowres = "force") against round 5's dispatch ("off": gather_gemm2 or
 im2col + the library GEMM on its recorded selection + col2im): forward, input gradient, weight gradient, each timed alone with
 HIP events.  One JSON line per layer.     python tools/bench_lowres.py [B]"""
 import json

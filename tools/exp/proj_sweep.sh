@@ -13,5 +13,4 @@ run "" ""
 for v in 512 768 1536; do run EML_WGRAD_WGS $v; done
 run "" ""
 for v in 32 128; do run EML_FUSED_MIN_MB $v; done
-run EML_WGRAD_LIB_KEPT 0
 run "" ""
