@@ -5,6 +5,7 @@ loss}.py`` with the same module names (hence the same ``state_dict`` keys: refer
 ``*_net_D.pth`` load) and forward signatures.  ``opt`` is any namespace with the reference's option names;
 ``default_options()`` gives the reference defaults (``options/base_options.py``, ``train_options.py``).
 """
+import argparse
 from argparse import Namespace
 
 import torch
@@ -22,7 +23,7 @@ def default_options(**kw):
                     norm_G="spectralspadesyncbatch3x3", norm_D="spectralinstance", norm_E="spectralinstance",
                     label_nc=3, output_nc=3, semantic_nc=3, num_D=2, n_layers_D=4, netD_subarch="n_layer",
                     no_ganFeat_loss=False, no_vgg_loss=True, gan_mode="hinge", lr=2e-4, beta1=0.0, beta2=0.9,
-                    no_TTUR=False, init_type="xavier", init_variance=0.02, isTrain=True)
+                    no_TTUR=False, init_type="xavier", init_variance=0.02, isTrain=True, lambda_render=0.0, render_size=32)
     for k, v in kw.items():
         setattr(opt, k, v)
     return opt
@@ -35,6 +36,24 @@ def add_vgg_arguments(ap):
     ap.add_argument("--vgg_random", action="store_true",
                     help="run the term on seeded RANDOM features: the reference's work (timing), not its objective")
     ap.add_argument("--no_vgg_loss", action="store_true", help="drop the term (also the default when no weights are given)")
+
+
+def _non_negative(text):
+    v = float(text)
+    if not v >= 0.0:
+        raise argparse.ArgumentTypeError("expected a number >= 0, got %r" % (text,))
+    return v
+
+
+def add_render_arguments(ap):
+    """The render-loss switches of the training entry points (``evaluate.RenderLoss``; not in the reference)."""
+    ap.add_argument("--lambda_render", type=_non_negative, default=0.0,
+                    help="weight of the sphere-render loss on the generator (what emlight_amd.evaluate scores); 0: off")
+    ap.add_argument("--render_size", type=int, default=32, help="sphere image size S of the render loss")
+
+
+def render_options(args):
+    return dict(lambda_render=float(args.lambda_render), render_size=int(args.render_size))
 
 
 def vgg_options(args, verbose=True):

@@ -17,6 +17,8 @@ Options of this build that the reference does not have: ``--synthetic --iters_pe
 (``data.ProjectorPanoramaBatcher``); the dataset / display flags are ignored there as under ``--synthetic``.
 ``--warp_move LO HI`` (train, with ``--pano_dir`` only): ``warped`` / ``map`` / ``input`` from the panorama warped to a drawn
 position along the view axis (``resize_exr``), as the reference's ``warpedHDROutputs`` files are.
+``--lambda_render L [--render_size S]`` (train): adds ``L`` times the sphere-render loss (``evaluate.RenderLoss``) to the
+generator's terms; 0, the default, leaves them as they are.
 """
 import argparse
 import os
@@ -164,7 +166,8 @@ def network_options(args, is_train=True, **extra):
         b2 = args.beta2 if args.beta2 is not None else (0.999 if args.no_TTUR else 0.9)
         kw.update(ndf=args.ndf, num_D=args.num_D, n_layers_D=args.n_layers_D, netD_subarch=args.netD_subarch,
                   no_ganFeat_loss=args.no_ganFeat_loss, gan_mode=args.gan_mode, lr=args.lr, beta1=b1, beta2=b2,
-                  no_TTUR=args.no_TTUR)
+                  no_TTUR=args.no_TTUR, lambda_render=getattr(args, "lambda_render", 0.0),
+                  render_size=getattr(args, "render_size", 32))
     kw.update(extra)
     for name, want in (("model", "pix2pix"), ("netG", "spade")) + ((("netD", "multiscale"), ("netD_subarch", "n_layer"),
                                                                     ("optimizer", "adam")) if is_train else ()):
@@ -187,6 +190,8 @@ def train_parser():
     add_pano_options(ap)
     from ..RegressionNetwork.data import add_warp_option
     add_warp_option(ap)
+    from .networks import add_render_arguments
+    add_render_arguments(ap)
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches (SURVEY 8d) instead of the Laval dataset")
     ap.add_argument("--iters_per_epoch", type=int, default=100, help="synthetic: iterations that make an epoch")
     ap.add_argument("--max_iters", type=int, default=0, help="stop after this many iterations (0: run niter + niter_decay epochs)")

@@ -3,7 +3,8 @@
 ``forward(data, mode)`` with ``mode in {'generator', 'discriminator', 'inference'}`` and the data dict keys
 ``input`` (Gaussian map, B,3,128,256), ``crop`` (B,3,128,128), ``warped`` (real HDR panorama), ``map`` (light mask).
 Loss terms as ``pix2pix_model.py:92-141``: hinge GAN, mask-weighted feature matching (x50 off the lights),
-cosine x5, VGG x5.  The VGG term (``vgg.py``) needs torchvision's pretrained VGG19 weights, which cannot be obtained
+cosine x5, VGG x5; with ``opt.lambda_render > 0`` (not in the reference; default 0: today's terms) also
+``Render`` = ``lambda_render * evaluate.RenderLoss(size=opt.render_size)(fake, real)``.  The VGG term (``vgg.py``) needs torchvision's pretrained VGG19 weights, which cannot be obtained
 offline (parity of the VALUE unpinned): with ``opt.no_vgg_loss`` False the feature stack is built from
 ``opt.vgg_weights`` (a torchvision ``vgg19`` state dict) or, when absent, from seeded random weights -- the step then does
 the reference's work.  A ``vgg_features`` callable may be passed instead.
@@ -182,7 +183,19 @@ class Pix2PixModel(torch.nn.Module):
             losses["VGG"] = vgg_loss(self.vgg_features, fake, real) * 5
         cos = torch.nn.CosineSimilarity(dim=1, eps=1e-20)
         losses["COS"] = (1 - cos(fake, real)).mean() * 5
+        lambda_render = getattr(self.opt, "lambda_render", 0.0)
+        if lambda_render > 0:
+            # what `python -m emlight_amd.evaluate` scores: the squared rmse of the sphere renders
+            losses["Render"] = lambda_render * self._render_loss()(fake, real)
         return losses, fake
+
+    def _render_loss(self):
+        crit = self.__dict__.get("_render_criterion")
+        if crit is None:
+            from ..evaluate import RenderLoss
+            crit = RenderLoss(size=getattr(self.opt, "render_size", 32))
+            object.__setattr__(self, "_render_criterion", crit)   # no parameters: kept out of the module tree
+        return crit
 
     # EML_GRAPH_DSTEP=0: A/B knob -- the discriminator step's generator pass eagerly, as in rounds 1-5
     graph_dstep = knob_flag("EML_GRAPH_DSTEP", True)

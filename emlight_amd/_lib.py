@@ -241,6 +241,11 @@ EXT_SIGNATURES = {
     # panorama warp (resize_exr): rotate, translate, resample with wrap-around
     "eml_pano_warp_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p,
                                  _f32p, _f64p, _stream]),
+    # render loss: the adjoint of the sphere renders (gradient with respect to the panorama) and the mirror's tap list
+    "eml_sphere_render_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int]),
+    "eml_sphere_render_bwd_f32": (_int, [_f32p, _int, _int, _int, _int, ctypes.c_double, _int, ctypes.c_double, _i32p, _i32p,
+                                         _f32p, _f32p, _f32p, _stream]),
+    "eml_sphere_mirror_taps_f32": (_int, [_int, _int, _int, ctypes.c_double, _i32p, _f32p, _stream]),
 }
 
 _lock = threading.Lock()

@@ -6,8 +6,13 @@ tree has no such code; DESIGN.md section 15 is the definition (``csrc/sphere_ren
 
 reads ``results/pred_<name>.npy`` as ``GenProjector.test --pano_dir`` writes them and scores each against the projector's
 target for that panorama (``ProjectorPanoramaBatcher(...)(pano, deg=0.0)["warped"]``: the panorama times the tonemap alpha).
+
+``render_spheres`` is differentiable in the panorama (the renders are linear in it; the gradient is the adjoint,
+``eml_sphere_render_bwd_f32``), and ``RenderLoss`` is the squared rmse of the renders as a training term: the projector and
+joint trainers add it with ``--lambda_render L [--render_size S]``.
 """
 import argparse
+import functools
 import json
 import os
 
@@ -45,30 +50,146 @@ def sphere_mask(size, device=None):
     return (X * X)[None, :] + (Y * Y)[:, None] < S * S
 
 
+def _pano_arg(pano, name, phong_exponent):
+    x = _lib.require_gpu_tensor(pano, name)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != 2 * x.shape[2]:
+        raise ValueError("%s: expected (B, 3, H, 2H), got %s" % (name, tuple(x.shape)))
+    if not float(phong_exponent) >= 0.0:
+        raise ValueError("phong_exponent must be >= 0, got %r" % (phong_exponent,))
+    return x
+
+
+def _canonical(names):
+    canon = [n for n in MATERIALS if n in names]                  # the kernel's order
+    return canon, sum(_BIT[n] for n in canon)
+
+
+def _render(x, S, mask, M, az, m):
+    """The forward's two calls: ``(B, 3, H, W)`` -> ``(B, M, 3, S, S)`` in the kernel's material order."""
+    B, _, H, W = x.shape
+    out = torch.empty(B, M, 3, S, S, dtype=torch.float32, device=x.device)
+    if B > 0:
+        L = _lib.lib()
+        work = torch.empty(max(1, L.eml_sphere_render_work_floats(B, H, W, S)), dtype=torch.float32, device=x.device)
+        _lib.check(L.eml_sphere_render_f32(_lib.ptr(x), B, H, W, S, az, mask, m, _lib.ptr(out), _lib.ptr(work),
+                                           _lib.current_stream()), "eml_sphere_render_f32")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _inside_count(S):
+    return int(sphere_mask(S).sum())                              # on the host: no device synchronisation
+
+
+_MIRROR_CSR = {}
+
+
+def _mirror_csr(H, W, S, az, device):
+    """The mirror's taps (``eml_sphere_mirror_taps_f32``: four per inside pixel) sorted by texel, as ``SphereGeometry`` sorts
+    its ``csr_*``: ``ptr (H W + 1)`` int32, ``src (4P)`` int32 linear pixel indices ``i S + j``, ``w (4P)`` float32.  A stable
+    sort, so a texel's entries keep the pixel order and the adjoint adds them in a fixed order.  Built once per geometry."""
+    key = (H, W, S, az, device)
+    got = _MIRROR_CSR.get(key)
+    if got is None:
+        P = _inside_count(S)
+        idx = torch.zeros(P, 4, dtype=torch.int32, device=device)
+        wgt = torch.zeros(P, 4, dtype=torch.float32, device=device)
+        _lib.check(_lib.lib().eml_sphere_mirror_taps_f32(H, W, S, az, _lib.ptr(idx), _lib.ptr(wgt), _lib.current_stream()),
+                   "eml_sphere_mirror_taps_f32")
+        flat = idx.reshape(-1).long()
+        order = torch.argsort(flat, stable=True)
+        pix = torch.nonzero(sphere_mask(S, device=device).reshape(-1)).reshape(-1)      # row-major: the kernels' pixel list
+        ptr = torch.zeros(H * W + 1, dtype=torch.int32, device=device)
+        ptr[1:] = torch.cumsum(torch.bincount(flat, minlength=H * W)[:H * W], 0)
+        got = _MIRROR_CSR[key] = (ptr, pix[order // 4].to(torch.int32).contiguous(), wgt.reshape(-1)[order].contiguous())
+    return got
+
+
+def _render_adjoint(g, B, H, W, S, mask, az, m):
+    """``eml_sphere_render_bwd_f32``: ``g (B, M, 3, S, S)`` in the kernel's material order -> ``(B, 3, H, W)``."""
+    g = _lib.require_gpu_tensor(g, "grad_out")
+    dpano = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
+    if B > 0:
+        L = _lib.lib()
+        work = torch.empty(max(1, L.eml_sphere_render_bwd_work_floats(B, H, W, S)), dtype=torch.float32, device=g.device)
+        csr = _mirror_csr(H, W, S, az, g.device) if mask & _BIT["mirror"] else (None, None, None)
+        _lib.check(L.eml_sphere_render_bwd_f32(_lib.ptr(g), B, H, W, S, az, mask, m, _lib.ptr(csr[0]), _lib.ptr(csr[1]),
+                                               _lib.ptr(csr[2]), _lib.ptr(dpano), _lib.ptr(work), _lib.current_stream()),
+                   "eml_sphere_render_bwd_f32")
+    return dpano
+
+
+class _RenderSpheres(torch.autograd.Function):
+    """The renders of ``pano`` and, in the same forward call, of ``truth`` (or None).  The operator is linear, so nothing is
+    saved but the geometry; ``truth``'s renders are not differentiable and the adjoint runs over ``pano``'s columns only."""
+
+    @staticmethod
+    def forward(ctx, pano, truth, S, mask, M, az, m):
+        B, _, H, W = pano.shape
+        ctx.geometry = (B, H, W, S, mask, az, m)
+        out = _render(pano if truth is None else torch.cat([pano, truth], 0), S, mask, M, az, m)
+        if truth is None:
+            return out
+        a, b = out[:B], out[B:]
+        ctx.mark_non_differentiable(b)
+        return a, b
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        return (_render_adjoint(g, *ctx.geometry),) + (None,) * 6
+
+
 def render_spheres(pano, size=64, materials=MATERIALS, view_azimuth_deg=180.0, phong_exponent=50.0):
     """``pano`` ``(B, 3, H, W)`` float32 on the device (``W == 2H``, the rasteriser's grid) -> ``(B, M, 3, S, S)``: the sphere
     under each of ``materials`` seen by an orthographic camera that looks towards ``view_azimuth_deg`` (180: the panorama's
     centre column); pixels outside the disc are 0.  ``eml_sphere_render_f32``; only enqueues work, run-to-run exact, and an
-    image's render does not depend on the batch it is in."""
+    image's render does not depend on the batch it is in.  Differentiable in ``pano`` (``eml_sphere_render_bwd_f32``: the
+    adjoint, with the same two properties); an input that does not require grad makes the forward's calls and nothing else."""
     names = _materials(materials)
     S = _size(size)
-    x = _lib.require_gpu_tensor(pano, "pano")
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != 2 * x.shape[2]:
-        raise ValueError("pano: expected (B, 3, H, 2H), got %s" % (tuple(x.shape),))
-    if not float(phong_exponent) >= 0.0:
-        raise ValueError("phong_exponent must be >= 0, got %r" % (phong_exponent,))
-    B, _, H, W = x.shape
-    canon = [n for n in MATERIALS if n in names]                  # the kernel's order
-    mask = sum(_BIT[n] for n in canon)
-    out = torch.empty(B, len(canon), 3, S, S, dtype=torch.float32, device=x.device)
-    if B > 0:
-        L = _lib.lib()
-        work = torch.empty(max(1, L.eml_sphere_render_work_floats(B, H, W, S)), dtype=torch.float32, device=x.device)
-        _lib.check(L.eml_sphere_render_f32(_lib.ptr(x), B, H, W, S, float(view_azimuth_deg), mask, float(phong_exponent),
-                                           _lib.ptr(out), _lib.ptr(work), _lib.current_stream()), "eml_sphere_render_f32")
+    x = _pano_arg(pano, "pano", phong_exponent)
+    canon, mask = _canonical(names)
+    args = (S, mask, len(canon), float(view_azimuth_deg), float(phong_exponent))
+    if torch.is_grad_enabled() and x.requires_grad:
+        out = _RenderSpheres.apply(x, None, *args)
+    else:
+        out = _render(x, *args)
     if list(names) != canon:
         out = torch.stack([out[:, canon.index(n)] for n in names], 1)     # slices, not an index tensor: no host-to-device copy
     return out
+
+
+class RenderLoss(torch.nn.Module):
+    """What the evaluation scores, as a training term: the mean over images and ``materials`` of ``sum (a - b)^2 / 3P`` with
+    ``a``, ``b`` the sphere renders of the prediction and of the truth and ``P`` the inside pixels -- the square of
+    ``render_metrics``' rmse.  Both batches go through ONE render call of ``2B`` images; the truth gets no gradient and the
+    adjoint kernel runs over the prediction's ``3B`` columns only.  After the first call of a geometry (the mirror's tap
+    table) a forward plus backward only enqueues work."""
+
+    def __init__(self, size=32, materials=("diffuse", "glossy"), view_azimuth_deg=180.0, phong_exponent=50.0):
+        super().__init__()
+        self.size, self.materials = _size(size), _materials(materials)
+        self.view_azimuth_deg, self.phong_exponent = float(view_azimuth_deg), float(phong_exponent)
+        if not self.phong_exponent >= 0.0:
+            raise ValueError("phong_exponent must be >= 0, got %r" % (phong_exponent,))
+
+    def forward(self, pred, true):
+        p = _pano_arg(pred, "pred", self.phong_exponent)
+        t = _pano_arg(true, "true", self.phong_exponent)
+        if p.shape != t.shape or p.shape[0] < 1:
+            raise ValueError("pred %s and true %s: expected two equal shapes (B, 3, H, 2H) with B >= 1"
+                             % (tuple(p.shape), tuple(t.shape)))
+        canon, mask = _canonical(self.materials)
+        B, M = p.shape[0], len(canon)
+        args = (self.size, mask, M, self.view_azimuth_deg, self.phong_exponent)
+        if torch.is_grad_enabled() and p.requires_grad:
+            a, b = _RenderSpheres.apply(p, t.detach(), *args)
+        else:
+            r = _render(torch.cat([p, t], 0), *args)
+            a, b = r[:B], r[B:]
+        d = a - b                                                         # 0 outside the disc: both renders are
+        return (d * d).sum() / (3.0 * _inside_count(self.size) * B * M)
 
 
 def render_metrics(pred_render, true_render):
@@ -98,7 +219,8 @@ def lighting_metrics(pred, true, size=64, materials=MATERIALS, view_azimuth_deg=
     if p.shape != t.shape:
         raise ValueError("pred %s and true %s differ in shape" % (tuple(p.shape), tuple(t.shape)))
     B = p.shape[0] if p.dim() == 4 else 0
-    r = render_spheres(torch.cat([p, t], 0), size, names, view_azimuth_deg, phong_exponent)
+    with torch.no_grad():                                             # scores, not a training term: see RenderLoss
+        r = render_spheres(torch.cat([p, t], 0), size, names, view_azimuth_deg, phong_exponent)
     m = render_metrics(r[:B], r[B:])
     return {"%s/%s" % (n, k): m[:, i, j] for i, n in enumerate(names) for j, k in enumerate(METRICS)}
 

@@ -137,6 +137,7 @@ def build_parser():
     ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
     add_warp_option(ap)
     networks.add_vgg_arguments(ap)
+    networks.add_render_arguments(ap)
     return ap
 
 
@@ -172,7 +173,8 @@ def main(argv=None):
     warp_move_range(args)             # before any process group exists: a flag that cannot apply exits at once
     rank, local, world = init_distributed()
     dev = "cuda:%d" % local
-    tr = JointTrainer(networks.default_options(ngf=args.ngf, ndf=args.ndf, **networks.vgg_options(args, verbose=rank == 0)),
+    tr = JointTrainer(networks.default_options(ngf=args.ngf, ndf=args.ndf, **networks.vgg_options(args, verbose=rank == 0),
+                                              **networks.render_options(args)),
                       anchors=args.anchors,
                       crop_hw=tuple(args.crop_hw), blur=args.blur, device=dev, world=world, reach=args.reach,
                       drop_rate=args.drop_rate)

@@ -41,6 +41,32 @@ extern "C" {
 int eml_pano_warp_f32(const float* pano, int B, int H, int W, int h, int w, double theta_deg, double phi_deg, double move,
                       const double* params_dev, float* out, double* coords, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- render loss: the adjoint of the sphere renders
+ * The reference tree has no such code; DESIGN.md section 15 is the definition (as for eml_sphere_render_f32, whose
+ * geometry, materials mask, material order and limits these share).  eml_sphere_render_f32 is linear in the panorama:
+ * two integrals K . pano and one bilinear lookup.  Its gradient with respect to the panorama is the adjoint:
+ *   dpano[b,ch,t] = sum_p Kd[p,t] g_d[b,ch,p] + sum_p Kg[p,t] g_g[b,ch,p] + sum over mirror taps (p,k) on t of w[p,k] g_m[b,ch,p]
+ * with Kd, Kg the weights of the two integrals, normalisations 1/pi and (m+1)/2pi included, p over the INSIDE pixels only
+ * (values of grad_out outside the disc are never read).
+ * grad_out (B,M,3,S,S) f32 in the kernel's material order (diffuse, glossy, mirror; M = bits set in materials_mask) ->
+ * dpano (B,3,H,W) f32, every element written.  K is never stored; no atomics: run-to-run exact; the summation is not split,
+ * pixels are added in list order, so an image's gradient has the same bits in any batch.
+ * With EML_SPHERE_MIRROR: the taps of eml_sphere_mirror_taps_f32 sorted by texel (stable) as a CSR over the H W texels:
+ * mirror_csr_ptr (H W + 1) int32, mirror_csr_src (4P) int32 = the pixel's linear index i S + j in the S x S image,
+ * mirror_csr_w (4P) f32; a texel's entries are added in CSR order after the integrals.  Entries outside [0, 4P) or
+ * [0, S S) are skipped.  Without that bit the three pointers are not read (NULL is fine).
+ * work: eml_sphere_render_bwd_work_floats(B, H, W, S) floats (0 when a size is refused or B == 0), 16-byte aligned. */
+size_t eml_sphere_render_bwd_work_floats(int B, int H, int W, int S);
+int eml_sphere_render_bwd_f32(const float* grad_out, int B, int H, int W, int S, double view_azimuth_deg, int materials_mask,
+                              double phong_m, const int* mirror_csr_ptr, const int* mirror_csr_src, const float* mirror_csr_w,
+                              float* dpano, float* work, eml_stream_t stream);
+
+/* The mirror's four taps per inside pixel (pixels in row-major order, P of them): idx (P,4) int32
+ * texel indices r W + c, wgt (P,4) f32.  Coordinates in f64 exactly as eml_sphere_render_f32 forms them (rows clamp,
+ * columns wrap); wx, wy rounded to f32, then (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy in f32 for the taps (r0,c0), (r0,c1),
+ * (r1,c0), (r1,c1).  Two taps of a pixel may name the same texel (a clamped row): they add. */
+int eml_sphere_mirror_taps_f32(int H, int W, int S, double view_azimuth_deg, int* idx, float* wgt, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
