@@ -21,10 +21,15 @@ import torch
 from torch.utils.data import Dataset
 
 
-def synthetic_batch(batch, anchors=128, crop_hw=(240, 320), seed=1234, device="cpu"):
+DEPTH_SEED_OFFSET = 7919   # the depth's own generator: seed + this, so the other tensors keep their bits
+
+
+def synthetic_batch(batch, anchors=128, crop_hw=(240, 320), seed=1234, device="cpu", with_depth=False):
     """One seeded synthetic batch: uniform crops, sparse-simplex distribution
     (mimics the >5%-of-max light mask of ``distribution_representation.py:96,110``),
-    intensity U(.05,2), unit-L2 rgb ratio, ambient U(0,.3)."""
+    intensity U(.05,2), unit-L2 rgb ratio, ambient U(0,.3).  ``with_depth``: also ``depth`` ``(batch, anchors)``, the
+    per-anchor scene depth of ``gmloss.SamplesLoss`` (reference ``data.py:75``), U(.5, 3) from a generator of its own:
+    every other tensor is the same with and without it."""
     g = torch.Generator().manual_seed(seed)
     crop = torch.rand(batch, 3, crop_hw[0], crop_hw[1], generator=g)
     d = torch.softmax(4.0 * torch.randn(batch, anchors, generator=g), dim=1)
@@ -36,18 +41,22 @@ def synthetic_batch(batch, anchors=128, crop_hw=(240, 320), seed=1234, device="c
     rgb = rgb / rgb.norm(dim=1, keepdim=True)
     ambient = torch.empty(batch, 3).uniform_(0.0, 0.3, generator=g)
     out = {"crop": crop, "distribution": d, "intensity": intensity, "rgb_ratio": rgb, "ambient": ambient}
+    if with_depth:
+        gd = torch.Generator().manual_seed(seed + DEPTH_SEED_OFFSET)
+        out["depth"] = torch.empty(batch, anchors).uniform_(0.5, 3.0, generator=gd)
     return {k: v.to(device) for k, v in out.items()}
 
 
 class SyntheticParameterDataset(Dataset):
-    def __init__(self, length=4096, anchors=128, crop_hw=(240, 320), seed=1234):
+    def __init__(self, length=4096, anchors=128, crop_hw=(240, 320), seed=1234, with_depth=False):
         self.length, self.anchors, self.crop_hw, self.seed = length, anchors, tuple(crop_hw), seed
+        self.with_depth = bool(with_depth)
 
     def __len__(self):
         return self.length
 
     def __getitem__(self, idx):
-        b = synthetic_batch(1, self.anchors, self.crop_hw, seed=self.seed + idx)
+        b = synthetic_batch(1, self.anchors, self.crop_hw, seed=self.seed + idx, with_depth=self.with_depth)
         item = {k: v[0] for k, v in b.items()}
         item["name"] = "synthetic_%06d" % idx
         return item
@@ -57,7 +66,8 @@ class PickleParameterDataset(Dataset):
     """``<dir>/<name>.pickle`` = {'distribution','intensity','rgb_ratio','ambient'} (the
     reference's GT format) next to ``<name>.npy`` = tonemapped crop (3,H,W) f32 in [0,1].
     Scaling follows ``data.py:70-73``: intensity*alpha/500, ambient*alpha/(128*256) with the
-    tonemap alpha stored in the pickle as 'alpha' (1.0 if absent)."""
+    tonemap alpha stored in the pickle as 'alpha' (1.0 if absent).  A pickle that holds 'depth' (the per-anchor scene
+    depth, ``data.py:75``) gives a ``depth`` item ``(N,)`` f32 as well; without it the key is absent."""
 
     def __init__(self, root):
         self.items = sorted(glob.glob(os.path.join(root, "*.pickle")))
@@ -73,12 +83,15 @@ class PickleParameterDataset(Dataset):
             p = pickle.load(f)
         alpha = float(p.get("alpha", 1.0))
         crop = np.load(path[:-len(".pickle")] + ".npy").astype(np.float32)
-        return {"crop": torch.from_numpy(crop),
+        item = {"crop": torch.from_numpy(crop),
                 "distribution": torch.as_tensor(p["distribution"], dtype=torch.float32),
                 "intensity": torch.as_tensor(p["intensity"], dtype=torch.float32).reshape(1) * alpha / 500.0,
                 "rgb_ratio": torch.as_tensor(p["rgb_ratio"], dtype=torch.float32),
                 "ambient": torch.as_tensor(p["ambient"], dtype=torch.float32) * alpha / (128 * 256),
                 "name": os.path.basename(path)[:-len(".pickle")]}
+        if "depth" in p:
+            item["depth"] = torch.as_tensor(np.asarray(p["depth"]), dtype=torch.float32).reshape(-1)
+        return item
 
 
 class PanoramaDataset(Dataset):

@@ -9,14 +9,23 @@ import torch.nn.functional as F
 
 from .DenseNet import DenseNet
 from .geomloss import SamplesLoss
+from .gmloss import SamplesLoss as GeometrySamplesLoss
 
 
 def regression_loss(pred, gt, sam_loss, ln):
     """``train.py:90-98``: 1000*sum(EMD) + 1000*MSE(dist) + .1*MSE(int) + 100*MSE(rgb) + MSE(amb)."""
     dist_pred = pred["distribution"].view(-1, ln, 1)
     dist_gt = gt["distribution"].view(-1, ln, 1)
+    if isinstance(sam_loss, GeometrySamplesLoss):   # GMLight: the ground cost of every sample from its scene's depth
+        if "depth" not in gt:
+            raise ValueError("the geometry-aware loss (gmloss.SamplesLoss) needs a per-anchor `depth` in every batch; this "
+                             "one has only %s -- use a dataset that returns it (SyntheticParameterDataset(with_depth=True), "
+                             "PickleParameterDataset over pickles that hold 'depth')" % sorted(gt))
+        emd = sam_loss(dist_pred, dist_gt, gt["depth"])
+    else:
+        emd = sam_loss(dist_pred, dist_gt)
     terms = {
-        "dist_emloss": sam_loss(dist_pred, dist_gt).sum() * 1000.0,
+        "dist_emloss": emd.sum() * 1000.0,
         "dist_l2loss": F.mse_loss(dist_pred, dist_gt) * 1000.0,
         "intensity_loss": F.mse_loss(pred["intensity"], gt["intensity"]) * 0.1,
         "rgb_loss": F.mse_loss(pred["rgb_ratio"], gt["rgb_ratio"]) * 100.0,
@@ -63,14 +72,16 @@ class RegressionTrainer:
 
     def __init__(self, anchors=96, crop_hw=(192, 256), blur=.025, diameter=None, lr=1e-4,
                  betas=(0.9, 0.999), device="cuda", world=1, bucket_cap_mb=64, model=None, sam_loss=None,
-                 sync_diameter=None, reach=None, drop_rate=0):
+                 sync_diameter=None, reach=None, drop_rate=0, geometry=False):
         """``model`` / ``sam_loss``: pre-built modules to train instead of the HIP ``DenseNet`` / ``SamplesLoss``
         (the CPU-only distributed tests inject the oracle's stock-op restatements; the product never does).
         ``sync_diameter``: derive the Sinkhorn eps-schedule from the range of the GLOBAL batch (2-float all-reduce per
         step) so that N ranks x B reproduce the single-process run with N*B samples (sinkhorn_divergence.py:9-18);
         default: on when world > 1 and no fixed ``diameter`` is given.
         ``reach``: unbalanced OT in the Sinkhorn criterion (``SamplesLoss(reach=...)``); None (default): balanced.
-        ``drop_rate``: the encoder's dropout (``DenseNet(drop_rate=...)``, DenseNet.py:50-55); 0 (default): none."""
+        ``drop_rate``: the encoder's dropout (``DenseNet(drop_rate=...)``, DenseNet.py:50-55); 0 (default): none.
+        ``geometry``: the criterion is ``gmloss.SamplesLoss`` (GMLight's geometric mover's loss) and every batch must carry
+        ``depth`` ``(B, anchors)``, one scene geometry per sample; ``sync_diameter`` holds for it as well."""
         from .._dist import dp_wrap, own_buckets, GradientBuckets
         if sync_diameter is None:
             sync_diameter = dp_wrap(world) and diameter is None
@@ -79,6 +90,9 @@ class RegressionTrainer:
         self.model = (DenseNet(anchors=anchors, crop_hw=crop_hw, drop_rate=drop_rate) if model is None
                       else model).to(self.device)
         self.model.train()
+        if sam_loss is None and geometry:
+            sam_loss = GeometrySamplesLoss("sinkhorn", p=2, blur=blur, reach=reach, diameter=diameter, anchors=anchors)
+            sam_loss.sync_diameter = bool(sync_diameter)
         self.sam_loss = sam_loss or SamplesLoss("sinkhorn", p=2, blur=blur, reach=reach, diameter=diameter,
                                                 anchors=anchors, sync_diameter=sync_diameter)
         self.ddp = self.buckets = None

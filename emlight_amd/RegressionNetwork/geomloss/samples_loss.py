@@ -19,6 +19,10 @@ Samples may be D-dimensional, ``(B, N, D)`` with ``1 <= D <= MAX_DIM`` as in the
 ``D = 1`` makes exactly the calls it always made, ``D > 1`` calls ``eml_sinkhorn_fwd_dim_f32``.  Weights passed in the
 four- or six-argument form get gradients when they require them: ``(b_x - a_x)`` and ``(a_y - b_y)`` of the final duals
 (``:65-69``; the weights enter the loop only through detached log-weights), ``eml_sinkhorn_bwd_weights_f32``.
+
+The ground cost may differ per sample: a ``(B, N, N)`` matrix (``forward(..., cost_matrix=)``, or what
+``gmloss.SamplesLoss`` builds from per-sample depths) goes to ``eml_sinkhorn_fwd_cost_f32`` with a stride of ``N*N`` floats;
+an ``(N, N)`` matrix makes exactly the calls it always made.
 """
 import math
 
@@ -185,9 +189,15 @@ def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=T
     ``flags``: EML_SINKHORN_* of the C ABI; default: whatever the split kernel's watch says (``_SplitWatch``).
     ``rho``: reach**p of unbalanced OT, or None (balanced; for 1-D points the call is ``eml_sinkhorn_fwd_ex_f32``, as
     it always was); ``want_lam``: also return the dampening schedule ``lam`` (64 floats next to ``eps_s``; all ones when
-    balanced)."""
+    balanced).
+    ``M, Mt``: ``(N, N)``, one ground cost for the batch, or ``(B, N, N)``, one per sample (``eml_sinkhorn_fwd_cost_f32``
+    with stride ``N*N``; the split kernel and its watch apply as with one matrix)."""
     L = _lib.lib()
     B, N = x.shape[:2]
+    per_sample = M.dim() == 3
+    if per_sample and (tuple(M.shape) != (B, N, N) or tuple(Mt.shape) != (B, N, N)):
+        raise ValueError("a per-sample ground cost must be (B, N, N) = (%d, %d, %d), got M %s and Mt %s"
+                         % (B, N, N, tuple(M.shape), tuple(Mt.shape)))
     D = x.shape[2] if x.dim() == 3 else None   # None: 1-D points through the entries that take no D
     o = out if out is not None else sinkhorn_outputs(B, N, x.device, need_gx, need_gy, D=D or 1)
     watched = D is None and flags is None and split_eligible(N)
@@ -203,7 +213,9 @@ def sinkhorn_raw(x, y, alpha, beta, M, Mt, p, blur, scaling, diameter, need_gx=T
             _lib.ptr(o["gx"]), _lib.ptr(o["gy"]), _lib.ptr(o["work"]), B, N)
     flags, stream = int(flags or 0), _lib.current_stream()
     rho_lam = (float(rho) if rho is not None else 0.0, _lib.ptr(lam))
-    if D is not None:
+    if per_sample:
+        _lib.check(L.eml_sinkhorn_fwd_cost_f32(*args, D or 1, flags, *rho_lam, N * N, stream), "eml_sinkhorn_fwd_cost_f32")
+    elif D is not None:
         _lib.check(L.eml_sinkhorn_fwd_dim_f32(*args, D, flags, *rho_lam, stream), "eml_sinkhorn_fwd_dim_f32")
     elif rho is None and not want_lam:
         _lib.check(L.eml_sinkhorn_fwd_ex_f32(*args, flags, stream), "eml_sinkhorn_fwd_ex_f32")
@@ -352,13 +364,25 @@ class SamplesLoss(Module):
             x, y = x.reshape(x.shape[0], self.N), y.reshape(x.shape[0], self.N)
         return _lib.require_gpu_tensor(x, "x"), _lib.require_gpu_tensor(y, "y")
 
-    def _cost_and_range(self, x, y):
+    def _call_cost(self, cost_matrix, x):
+        """``forward(..., cost_matrix=)``: an ``(N, N)`` or ``(B, N, N)`` f32 device tensor that stands in for the
+        module's matrix for one call, as ``(M, Mt)``."""
+        M = _lib.require_gpu_tensor(cost_matrix, "cost_matrix")
+        B = x.shape[0]
+        if tuple(M.shape) not in ((self.N, self.N), (B, self.N, self.N)):
+            raise ValueError("cost_matrix must be (N, N) or (B, N, N) with B = %d, N = %d; got %s"
+                             % (B, self.N, tuple(M.shape)))
+        return M, M.transpose(-1, -2).contiguous()
+
+    def _cost_and_range(self, x, y, cost_matrix=None):
         """The cost matrices on the samples' device and, under ``sync_diameter``, the range of the global batch
         (``(2,)``, or ``(2*D,)`` for D > 1)."""
-        M, Mt = self.cost_matrix(x.device)
+        M, Mt = self.cost_matrix(x.device) if cost_matrix is None else self._call_cost(cost_matrix, x)
         return M, Mt, global_range(x, y) if (self.sync_diameter and self.diameter is None) else None
 
-    def forward(self, *args):
+    def forward(self, *args, cost_matrix=None):
+        """``cost_matrix``: an ``(N, N)`` or per-sample ``(B, N, N)`` f32 device tensor used instead of the module's
+        matrix for this call (no gradient reaches it: the reference detaches M, ``gmloss/utils.py:104``)."""
         a, x, b, y = self.process_args(*args)
         self._check_samples(x, y)
         x, y = self._samples(x, y)
@@ -367,16 +391,16 @@ class SamplesLoss(Module):
             return x.new_zeros(0) + 0.0 * (x.sum() + y.sum())
         a = None if a is None else _lib.require_gpu_tensor(a.reshape(B, self.N), "alpha")
         b = None if b is None else _lib.require_gpu_tensor(b.reshape(B, self.N), "beta")
-        M, Mt, rng = self._cost_and_range(x, y)
+        M, Mt, rng = self._cost_and_range(x, y, cost_matrix)
         return _SinkhornDivergence.apply(x, y, a, b, M, Mt, self.p, self.blur, self.scaling, self.diameter, rng, self.rho)
 
-    def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None, want_lam=False):
+    def forward_raw(self, x, y, need_gx=True, need_gy=True, out=None, flags=None, want_lam=False, cost_matrix=None):
         """Every device output of one call (loss, unit grads, schedule, duals; with ``want_lam`` the dampening schedule
         ``lam`` next to ``eps_s``) -- for parity tests and timing.  1-D points may come as ``(B, N)`` or ``(B, N, 1)``;
-        ``(B, N, D)`` samples with D > 1 give gradients ``(B, N, D)``."""
+        ``(B, N, D)`` samples with D > 1 give gradients ``(B, N, D)``.  ``cost_matrix``: as in ``forward``."""
         if x.dim() == 3 and x.shape[-1] > 1:
             self._check_samples(x, y)
         x, y = self._samples(x, y)
-        M, Mt, rng = self._cost_and_range(x, y)
+        M, Mt, rng = self._cost_and_range(x, y, cost_matrix)
         return sinkhorn_raw(x, y, None, None, M, Mt, self.p, self.blur, self.scaling, self.diameter,
                             need_gx, need_gy, out, range_lo_hi=rng, flags=flags, rho=self.rho, want_lam=want_lam)

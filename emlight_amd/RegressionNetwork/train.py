@@ -5,6 +5,7 @@ torchrun-aware, same optimiser, loss weights, print/visualise/checkpoint cadence
     python -m emlight_amd.RegressionNetwork.train --synthetic --epochs 1
     torchrun --nproc-per-node 8 -m emlight_amd.RegressionNetwork.train --synthetic
     python -m emlight_amd.RegressionNetwork.train --pano_dir DIR --fov 60 [--warp_move -0.6 0]      # crops and targets made on the GPU per step
+    python -m emlight_amd.RegressionNetwork.train --synthetic --geometry --anchors 128                # GMLight's loss, one scene depth per sample
 """
 import argparse
 import os
@@ -62,8 +63,22 @@ def build_parser():
                     help="directory of *.npy HDR panoramas (H, W, 3): every step crops a fresh random view of each panorama, "
                          "tonemaps it and derives the targets on the GPU (data.PanoramaBatcher); overrides --train_dir")
     ap.add_argument("--fov", type=float, default=60.0, help="field of view of the --pano_dir crops, degrees")
+    ap.add_argument("--geometry", action="store_true",
+                    help="GMLight's geometric mover's loss (gmloss.SamplesLoss): the Sinkhorn ground cost of every sample from "
+                         "its scene's per-anchor depth, which the dataset must return (--synthetic draws one; --train_dir "
+                         "pickles must hold 'depth'); not with --pano_dir, which has no depth panoramas")
     data.add_warp_option(ap)
     return ap
+
+
+def parse_args(argv=None):
+    """``build_parser().parse_args`` plus the combinations that are refused at parsing."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.geometry and args.pano_dir:
+        ap.error("--geometry needs a per-anchor depth for every sample and --pano_dir has no depth panoramas to derive it "
+                 "from: use --synthetic or a --train_dir whose pickles hold 'depth'")
+    return args
 
 
 def make_batcher(args, device):
@@ -78,14 +93,15 @@ def make_batcher(args, device):
 def main(argv=None):
     from emlight_amd import _runtime
     _runtime.entry_point_defaults()   # kernel arguments in device memory, recorded library-GEMM selection: an entry point's choice
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     data.warp_move_range(args)        # before any process group exists: a flag that cannot apply exits at once
 
     rank, local, world = init_distributed()
     device = "cuda:%d" % local
     tr = RegressionTrainer(anchors=args.anchors, crop_hw=tuple(args.crop_hw), blur=args.blur,
                            diameter=args.diameter, reach=args.reach, drop_rate=args.drop_rate, device=device, world=world,
-                           sync_diameter=None if args.sync_diameter is None else bool(args.sync_diameter))
+                           sync_diameter=None if args.sync_diameter is None else bool(args.sync_diameter),
+                           geometry=args.geometry)
     if args.load:
         tr.model.load_state_dict(torch.load(args.load, map_location=device))
         if rank == 0:
@@ -94,7 +110,7 @@ def main(argv=None):
     if batcher is not None:
         ds = data.PanoramaDataset(args.pano_dir)
     elif args.synthetic or not args.train_dir:
-        ds = data.SyntheticParameterDataset(anchors=args.anchors, crop_hw=tuple(args.crop_hw))
+        ds = data.SyntheticParameterDataset(anchors=args.anchors, crop_hw=tuple(args.crop_hw), with_depth=args.geometry)
     else:
         ds = data.PickleParameterDataset(args.train_dir)
     sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None

@@ -246,6 +246,11 @@ EXT_SIGNATURES = {
     "eml_sphere_render_bwd_f32": (_int, [_f32p, _int, _int, _int, _int, ctypes.c_double, _int, ctypes.c_double, _i32p, _i32p,
                                          _f32p, _f32p, _f32p, _stream]),
     "eml_sphere_mirror_taps_f32": (_int, [_int, _int, _int, ctypes.c_double, _i32p, _f32p, _stream]),
+    # GMLight loss with one scene geometry per sample: batched anchors + chord matrices, Sinkhorn with a cost stride
+    "eml_gm_anchor_cost_f32": (_int, [ctypes.c_void_p, _int, _int, _int, _f32p, _f32p, _stream]),
+    "eml_sinkhorn_fwd_cost_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_double, ctypes.c_double, _int,
+                                         ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
+                                         _int, _int, ctypes.c_double, _f32p, ctypes.c_long, _stream]),
 }
 
 _lock = threading.Lock()

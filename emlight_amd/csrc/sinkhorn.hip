@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
     double blur, double log_blur, double log_scaling, int p_exp, double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out,
     int* __restrict__ n_eps_out, float* __restrict__ diameter_out, double rho, float* __restrict__ lam_out,
     float* __restrict__ work /* (8,B,N): duals a_x,b_y,a_y,b_x then E rows; kD > 1: (4,B,N) duals, (4,B,N,dim) E rows */,
-    int B, int N, int dim) {
+    int B, int N, int dim, long cost_stride /* floats between the samples' chord matrices; 0: one matrix for the batch */) {
   constexpr int kGT = kCached ? 512 : 256;  // threads per softmin group
   constexpr int kWG = 2 * kGT;              // two groups per workgroup
   // LDS vectors ahead of lw2: pts (kD = 1); pts + nrm (cached, kD > 1); nrm (stream, kD > 1)
@@ -277,6 +277,8 @@ __global__ __launch_bounds__(kCached ? 1024 : 512) void sinkhorn_loop_kernel(
 
   const int b = blockIdx.x >> 1;
   const int role = blockIdx.x & 1;     // 0: (xx, yy)   1: (yx, xy)
+  M += (size_t)b * cost_stride;        // this sample's ground cost (gmloss: one chord matrix per scene)
+  Mt += (size_t)b * cost_stride;
   const int tid = threadIdx.x;
   const int gl = tid / kGT;            // local group 0/1; its columns are x for gl = 0 and y for gl = 1 in both roles
   const int g = 2 * role + gl;         // global problem id 0..3
@@ -661,7 +663,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
     int p_exp,
     double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out, int* __restrict__ n_eps_out, float* __restrict__ diameter_out,
     double rho, float* __restrict__ lam_out, float* __restrict__ work, int B, int N, const int* __restrict__ only_if,
-    int dim) {
+    int dim, long cost_stride) {
   // `only_if` (device, may be NULL): the RESCUE launch behind the split kernel -- it returns at once unless the split
   // kernel raised its status word (a slice never saw its partners), in which case it recomputes the whole batch here
   if (only_if && __hip_atomic_load(only_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -685,6 +687,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_loop_tiled_kernel(
   float* Mtile = qq + 2 * NP;              // [2][NR][TS]
 
   const int b = blockIdx.x >> 1, role = blockIdx.x & 1, tid = threadIdx.x;
+  M += (size_t)b * cost_stride;   // this sample's ground cost; the launcher keeps the stride a multiple of 4 (float4 loads)
   const int gl = tid / kGT, g = 2 * role + gl, t = tid & (kGT - 1);
   const bool rows_x = (g == 0 || g == 3), cols_x = (g == 0 || g == 2);
   const int consumer_l = role ? (1 - gl) : gl;
@@ -946,7 +949,8 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
     const float* __restrict__ alpha, const float* __restrict__ beta, double blur, double log_blur, double log_scaling,
     int p_exp, double diameter, const float* __restrict__ range_dev, float* __restrict__ eps_out,
     int* __restrict__ n_eps_out, float* __restrict__ diameter_out, double rho, float* __restrict__ lam_out,
-    float* __restrict__ work, unsigned long long* __restrict__ exch, int B, int S, int* __restrict__ status, int test_stall) {
+    float* __restrict__ work, unsigned long long* __restrict__ exch, int B, int S, int* __restrict__ status, int test_stall,
+    long cost_stride) {
   constexpr int N = CPL * kSplitLPR, kWG = 16 * R, kGT = 8 * R, LDM = N + 32;   // LDM = 32 mod 64: two rows cover all banks
   static_assert(CPL % 4 == 0 && N % 64 == 0 && kWG <= 1024, "split kernel geometry");
   __shared__ float eps_l[EML_MAX_EPS];
@@ -962,6 +966,7 @@ __global__ __launch_bounds__(16 * R) void sinkhorn_loop_split_kernel(
   const int tid = threadIdx.x;
   const int slice = blockIdx.x % S, br = blockIdx.x / S, b = br >> 1, role = br & 1;
   const int r0 = slice * R;
+  M += (size_t)b * cost_stride;   // this sample's ground cost (a multiple of 4 floats: float4 loads below)
   const ScanHead scan_head = schedule_scan_begin<kWG>(x, y, B, N, diameter, range_dev);
   // this workgroup's rows of the chord matrix: requested before anything waits, committed below
   constexpr int kM4 = R * N / 4 / kWG;     // float4 per thread: R * N / (64 R) = N / 64
@@ -1199,6 +1204,52 @@ __global__ __launch_bounds__(256) void anchor_cost_kernel(const float* __restric
   M[idx] = sqrtf(dx * dx + dy * dy + dz * dz);
 }
 
+// GMLight's ground cost for a batch of scenes: depth (B,N) -> depth-scaled Fibonacci anchors (B,N,3) and their chord
+// matrices (B,N,N) in one launch (gmloss/utils.py:63-92, one `distance` per sample).  A workgroup owns kGmRows rows of one
+// sample's matrix: it builds that sample's N anchors in LDS -- f64 like numpy (theta = golden_angle * k, z = linspace(1 - 1/N,
+// 1/N - 1, N) as numpy forms it: k * step + start in two roundings, the last element the stop itself), the f32 or f64 depth
+// promoted exactly, each coordinate rounded to f32 once -- and then writes its rows with anchor_cost_kernel's arithmetic, the
+// order of the sum fixed: dx_ij = -dx_ji exactly, so M is symmetric bit for bit and its diagonal is +0.
+constexpr int kGmRows = 8;
+constexpr int kGmMaxN = 2048;
+__global__ __launch_bounds__(256) void gm_anchor_cost_kernel(const void* __restrict__ depth, int depth_is_f64, int N,
+                                                             int tiles, float* __restrict__ anchors_out,
+                                                             float* __restrict__ M_out) {
+  __shared__ float al[3 * kGmMaxN];
+  const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles, tid = threadIdx.x;
+  const double golden = M_PI * (3.0 - 2.23606797749979 /* sqrt(5) in f64 */);
+  const double start = 1.0 - 1.0 / N, stop = 1.0 / N - 1.0;
+  const double step = N > 1 ? (stop - start) / (double)(N - 1) : 0.0;
+  for (int k = tid; k < N; k += 256) {
+    const size_t o = (size_t)b * N + k;
+    const double r = depth_is_f64 ? static_cast<const double*>(depth)[o] : (double)static_cast<const float*>(depth)[o];
+    const double theta = __dmul_rn(golden, (double)k);
+    double z = __dadd_rn(__dmul_rn((double)k, step), start);
+    if (N > 1 && k == N - 1) z = stop;
+    const float ax = (float)__dmul_rn(r, cos(theta)), ay = (float)__dmul_rn(r, sin(theta)), az = (float)z;
+    al[3 * k] = ax;
+    al[3 * k + 1] = ay;
+    al[3 * k + 2] = az;
+    if (tile == 0 && anchors_out) {
+      anchors_out[3 * o] = ax;
+      anchors_out[3 * o + 1] = ay;
+      anchors_out[3 * o + 2] = az;
+    }
+  }
+  __syncthreads();
+  const int r0 = tile * kGmRows, rows = min(kGmRows, N - r0);
+  float* Mb = M_out + (size_t)b * N * N + (size_t)r0 * N;
+  const float* a = al;
+  for (int e = tid; e < rows * N; e += 256) {
+#pragma clang fp contract(off)
+    const int i = r0 + e / N, j = e % N;
+    const float dx = a[3 * i] - a[3 * j], dy = a[3 * i + 1] - a[3 * j + 1], dz = a[3 * i + 2] - a[3 * j + 2];
+    // anchor_cost_kernel's sum as it is compiled -- fma(dx, dx, dy^2) + dz^2 -- spelled out, contraction off: left to the
+    // compiler, the unrolled loop contracts its elements in different orders and M_ij != M_ji in the last bit
+    Mb[e] = sqrtf(fmaf(dx, dx, dy * dy) + dz * dz);
+  }
+}
+
 // Diameter (range of x U y) + epsilon schedule, all on the device.
 __global__ __launch_bounds__(1024) void schedule_kernel(const float* __restrict__ x,
                                                         const float* __restrict__ y, long n,
@@ -1410,6 +1461,7 @@ struct SinkhornCall {
   double rho;
   float* lam_out;
   hipStream_t stream;
+  long cost_stride = 0;   // floats between the samples' M (and Mt); 0: one matrix for the batch (eml_sinkhorn_fwd_cost_f32)
   double log_blur = 0.0, log_scaling = 0.0;   // f64 like numpy (only log(diameter) is data); set once the call is checked
 };
 
@@ -1426,20 +1478,20 @@ template <auto Kernel>
 void enqueue_loop(const SinkhornCall& c, int block, size_t lds) {
   launch<Kernel>(dim3(2 * c.B), dim3(block), lds, c.stream, c.x, c.y, c.M, c.Mt, c.alpha, c.beta, c.blur, c.log_blur,
                  c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
-                 c.work, c.B, c.N, c.D);
+                 c.work, c.B, c.N, c.D, c.cost_stride);
 }
 // `only_if`: see the kernel (the rescue launch behind the split kernel)
 template <auto Kernel>
 void enqueue_tiled(const SinkhornCall& c, size_t lds, const int* only_if) {
   launch<Kernel>(dim3(2 * c.B), dim3(1024), lds, c.stream, c.x, c.y, c.M, c.alpha, c.beta, c.blur, c.log_blur,
                  c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
-                 c.work, c.B, c.N, only_if, c.D);
+                 c.work, c.B, c.N, only_if, c.D, c.cost_stride);
 }
 template <auto Kernel>
 void enqueue_split(const SinkhornCall& c, int S, int R, size_t lds, unsigned long long* exch, int* status) {
   launch<Kernel>(dim3(2 * c.B * S), dim3(16 * R), lds, c.stream, c.x, c.y, c.M, c.alpha, c.beta, c.blur, c.log_blur,
                  c.log_scaling, c.p, c.diameter, c.range_lo_hi, c.eps_out, c.n_eps_out, c.diameter_out, c.rho, c.lam_out,
-                 c.work, exch, c.B, S, status, (c.flags & EML_SINKHORN_TEST_STALL) ? 1 : 0);
+                 c.work, exch, c.B, S, status, (c.flags & EML_SINKHORN_TEST_STALL) ? 1 : 0, c.cost_stride);
 }
 
 // LDS-tiled kernel: chord-matrix column tiles (8192 floats, double-buffered) shared by both problems of a workgroup
@@ -1554,6 +1606,12 @@ int sinkhorn_forward(SinkhornCall c) {
   if (c.B < 0 || c.N < 1 || c.N > 2048) return eml::fail(EML_EINVAL, "%s: need 1<=N<=2048 (got %d)", c.who, c.N);
   if (!(c.blur > 0.0) || !(c.scaling > 0.0 && c.scaling < 1.0) || c.p < 1)
     return eml::fail(EML_EINVAL, "%s: need blur>0, 0<scaling<1, p>=1", c.who);
+  if (c.cost_stride < 0 || (c.cost_stride > 0 && c.cost_stride < (long)c.N * c.N))
+    return eml::fail(EML_EINVAL, "%s: cost_stride must be 0 (one matrix) or >= N*N = %ld floats (got %ld)", c.who,
+                     (long)c.N * c.N, c.cost_stride);
+  if ((c.N & 3) == 0 && (c.cost_stride & 3) != 0)   // the tiled and split kernels load M as 16-byte vectors
+    return eml::fail(EML_EINVAL, "%s: cost_stride must be a multiple of 4 floats when N %% 4 == 0 (got %ld)", c.who,
+                     c.cost_stride);
   if (int rc = refuse_long_schedule(c.who, c.p, c.diameter, c.blur, c.scaling)) return rc;
   if (c.B == 0) return EML_OK;
   c.log_blur = std::log(c.blur);
@@ -1646,6 +1704,34 @@ extern "C" int eml_sinkhorn_fwd_dim_f32(const float* x, const float* y, const fl
   return sinkhorn_forward({"eml_sinkhorn_fwd_dim_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
                            eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, D, flags, rho, lam_out,
                            (hipStream_t)stream});
+}
+
+// eml_sinkhorn_fwd_dim_f32 with one ground cost per sample: sample b reads M + b * cost_stride (and Mt likewise).
+extern "C" int eml_sinkhorn_fwd_cost_f32(const float* x, const float* y, const float* M, const float* Mt,
+                                         const float* alpha, const float* beta, double blur, double scaling, int p,
+                                         double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                                         float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                                         int D, int flags, double rho, float* lam_out, long cost_stride,
+                                         eml_stream_t stream) {
+  if (D < 1 || D > EML_SINKHORN_MAX_DIM)
+    return eml::fail(EML_EINVAL, "eml_sinkhorn_fwd_cost_f32: need 1 <= D <= %d (got %d)", EML_SINKHORN_MAX_DIM, D);
+  return sinkhorn_forward({"eml_sinkhorn_fwd_cost_f32", x, y, M, Mt, alpha, beta, blur, scaling, p, diameter, range_lo_hi,
+                           eps_out, n_eps_out, diameter_out, loss, gx, gy, work, B, N, D, flags, rho, lam_out,
+                           (hipStream_t)stream, cost_stride});
+}
+
+extern "C" int eml_gm_anchor_cost_f32(const void* depth, int depth_is_f64, int B, int N, float* anchors_out, float* M_out,
+                                      eml_stream_t stream) {
+  if (B < 0 || N < 1 || N > kGmMaxN)
+    return eml::fail(EML_EINVAL, "eml_gm_anchor_cost_f32: need B >= 0, 1 <= N <= %d (got B = %d, N = %d)", kGmMaxN, B, N);
+  if (!depth || !M_out) return eml::fail(EML_EINVAL, "eml_gm_anchor_cost_f32: null pointer");
+  if (B == 0) return EML_OK;
+  const int tiles = (N + kGmRows - 1) / kGmRows;
+  if ((long)B * tiles > (long)INT32_MAX)
+    return eml::fail(EML_EINVAL, "eml_gm_anchor_cost_f32: B * ceil(N / %d) exceeds 2^31 - 1 workgroups", kGmRows);
+  hipLaunchKernelGGL(gm_anchor_cost_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream, depth,
+                     depth_is_f64 ? 1 : 0, N, tiles, anchors_out, M_out);
+  return eml::check_launch("eml_gm_anchor_cost_f32");
 }
 
 extern "C" int eml_sinkhorn_bwd_weights_f32(const float* gloss, const float* work, float* galpha, float* gbeta, int B,

@@ -67,6 +67,32 @@ int eml_sphere_render_bwd_f32(const float* grad_out, int B, int H, int W, int S,
  * (r1,c0), (r1,c1).  Two taps of a pixel may name the same texel (a clamped row): they add. */
 int eml_sphere_mirror_taps_f32(int H, int W, int S, double view_azimuth_deg, int* idx, float* wgt, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- GMLight loss: one scene geometry per sample
+ * gmloss/utils.py:63-108 (`geometric_points` and `distance`, built once per sample instead of one geometry repeated
+ * `batchsize` times, utils.py:89-93).  depth (B,N): the per-anchor depths, f32 or f64 (depth_is_f64 != 0), device ->
+ *   anchors_out (B,N,3) f32 or NULL: (r cos theta, r sin theta, z) with theta = pi (3 - sqrt 5) k and
+ *     z = linspace(1 - 1/N, 1/N - 1, N), evaluated in f64 as numpy does (an f32 depth is promoted exactly) and rounded to f32 once;
+ *   M_out (B,N,N) f32: M_ij = sqrtf(dx^2 + dy^2 + dz^2) of the f32 anchors, eml_emd_anchor_cost_f32's arithmetic; the
+ *     diagonal is exactly 0 and M is symmetric bit for bit.
+ * One launch for the batch, no host work per sample, no atomics.  Limits: 1 <= N <= 2048, B >= 0 (B == 0 returns 0);
+ * a NULL depth or M_out is EML_EINVAL before anything is enqueued. */
+int eml_gm_anchor_cost_f32(const void* depth, int depth_is_f64, int B, int N, float* anchors_out, float* M_out,
+                           eml_stream_t stream);
+
+/* gmloss/samples_loss.py:69-84 (`sinkhorn_tensorized` with a `distance` per call) on a batch whose samples each have
+ * their own ground cost: eml_sinkhorn_fwd_dim_f32, every argument and output as there, plus
+ *   cost_stride   floats between the samples' matrices: sample b reads M + b * cost_stride and Mt + b * cost_stride
+ *                 ((B,N,N) contiguous: N*N).  0: one (N,N) matrix for the batch -- the outputs of eml_sinkhorn_fwd_dim_f32
+ *                 bit for bit.
+ * EML_EINVAL, with nothing enqueued: cost_stride < 0; 0 < cost_stride < N*N; cost_stride % 4 != 0 when N % 4 == 0 (those
+ * kernels load M as 16-byte vectors, so M itself must be 16-byte aligned as well).  The split kernel, its status word
+ * and its rescue launch, rho, D > 1 and the weight gradients work as with one matrix. */
+int eml_sinkhorn_fwd_cost_f32(const float* x, const float* y, const float* M, const float* Mt,
+                              const float* alpha, const float* beta, double blur, double scaling, int p,
+                              double diameter, const float* range_lo_hi, float* eps_out, int* n_eps_out,
+                              float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
+                              int D, int flags, double rho, float* lam_out, long cost_stride, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,10 @@ split kernel), blur .05, the inputs of bench.py's Sinkhorn leg.
 
 ``--dim``: instead of balanced vs damped, balanced calls on (B, N, D) samples for D in {1, 2, 4, 8} (eml_sinkhorn_fwd_dim_f32
 for D > 1), alternating window by window the same way.
+
+``--per_sample``: one shared (N, N) chord matrix (eml_sinkhorn_fwd_ex_f32) against one matrix per sample (B, N, N)
+(eml_sinkhorn_fwd_cost_f32, stride N*N; the matrices of depths U(.5, 3) as gmloss.SamplesLoss builds them), and the batched
+builder eml_gm_anchor_cost_f32 on its own, alternating the same way.
 """
 import argparse
 import json
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--dim", action="store_true", help="time D = 1, 2, 4, 8 samples instead of balanced vs damped")
+    ap.add_argument("--per_sample", action="store_true",
+                    help="time a shared chord matrix against one per sample, and the batched cost builder")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sinkhorn.py needs the MI355X")
@@ -45,7 +51,25 @@ def main():
         x = torch.softmax(torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
         y = torch.softmax(3 * torch.randn(B, N, generator=g), 1).view(B, N, 1).to(dev)
         calls = {}
-        if a.dim:
+        if a.per_sample:
+            from emlight_amd import _lib
+            from emlight_amd.RegressionNetwork.geomloss.samples_loss import sinkhorn_raw
+            crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, anchors=N)
+            M1, _ = crit.cost_matrix(dev)
+            depth = torch.empty(B, N).uniform_(.5, 3., generator=g).to(dev)
+            anchors, Mb = torch.empty(B, N, 3, device=dev), torch.empty(B, N, N, device=dev)
+
+            def build():
+                _lib.check(_lib.lib().eml_gm_anchor_cost_f32(_lib.ptr(depth), 0, B, N, _lib.ptr(anchors), _lib.ptr(Mb),
+                                                             _lib.current_stream()), "eml_gm_anchor_cost_f32")
+                return None
+            build()
+            xr, yr = x.view(B, N).contiguous(), y.view(B, N).contiguous()
+            for label, M in (("shared", M1), ("per_sample", Mb)):
+                out = sinkhorn_outputs(B, N, dev, True, True)
+                calls[label] = (lambda M=M, out=out: sinkhorn_raw(xr, yr, None, None, M, M, 2, a.blur, .5, None, True, True,
+                                                                  out=out))
+        elif a.dim:
             crit = SamplesLoss("sinkhorn", p=2, blur=a.blur, anchors=N)
             for D in (1, 2, 4, 8):
                 # component 0 is the 1-D input; the others are further draws of the same recipe
@@ -61,6 +85,8 @@ def main():
                 out = sinkhorn_outputs(B, N, dev, True, True)
                 calls[label] = (lambda crit=crit, out=out: crit.forward_raw(x, y, out=out))
         n_eps = int(next(iter(calls.values()))()["n_eps"].item())
+        if a.per_sample:
+            calls["builder"] = build
         for fn in calls.values():
             for _ in range(20):
                 fn()
@@ -76,12 +102,14 @@ def main():
                 torch.cuda.synchronize()
                 us[k].append(1e3 * e0.elapsed_time(e1) / a.reps)
         row = {"shape": name, "B": B, "N": N, "n_eps": n_eps}
-        if not a.dim:
+        if not a.dim and not a.per_sample:
             row["reach"] = a.reach
         for k, v in us.items():
             row[k + "_us"] = round(float(np.median(v)), 2)
             row[k + "_us_min_max"] = [round(float(min(v)), 2), round(float(max(v)), 2)]
-        if a.dim:
+        if a.per_sample:
+            row["per_sample_over_shared"] = round(row["per_sample_us"] / row["shared_us"], 4)
+        elif a.dim:
             for D in (2, 4, 8):
                 row["D%d_over_D1" % D] = round(row["D%d_us" % D] / row["D1_us"], 4)
         else:
