@@ -15,7 +15,7 @@ from torch.nn.utils import spectral_norm
 
 from . import spherenet
 from .._knobs import knob_flag
-from .spherenet import SphereConv2D
+from .spherenet import SphereConv2D, SphereMaxPool2D  # noqa: F401  (both names of the reference's spherenet package)
 
 
 def default_options(**kw):

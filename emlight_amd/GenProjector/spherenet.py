@@ -611,6 +611,67 @@ def planar_conv3x3(x, weight, bias, stride=1, act_slope=1.0):
     return _SphereConvFn.apply(x, weight, bias, stride, "planar", None, act_slope)
 
 
+class _SphereMaxPoolFn(torch.autograd.Function):
+    """``max_pool2d(grid_sample(x, grid), 3, 3)`` (``sphere_cnn.py:139-150``) in one HIP pass over the tap table
+    (``csrc/sphere_pool.hip``): the maximum of the nine bilinear taps with the winning tap ``a*3 + b`` as one byte per output
+    element; the backward gathers over the table's CSR transpose, routed by those bytes -- no 9x tensor, no atomics.
+    Returns (y, indices); ``indices`` is None unless ``keep`` (a gradient or ``return_indices`` needs them)."""
+
+    @staticmethod
+    def forward(ctx, x, stride, keep):
+        from .. import _lib
+        _require_gpu_f32(x, "SphereMaxPool2D input")
+        if x.dim() != 4:
+            raise ValueError("SphereMaxPool2D takes a (B, C, H, W) tensor, got %s" % (tuple(x.shape),))
+        L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
+        B, C, H, W = x.shape
+        geo = sphere_geometry(H, W, stride, x.device, "sphere")
+        po = geo.ho * geo.wo
+        xr = _aligned16(x.permute(0, 2, 3, 1).contiguous())       # (B,H,W,C); a view when x is channels-last
+        y = torch.empty(B, geo.ho, geo.wo, C, dtype=torch.float32, device=x.device)
+        arg = torch.empty(B, geo.ho, geo.wo, C, dtype=torch.uint8, device=x.device) if keep else None
+        _lib.check(L.eml_sphere_max_pool_fwd_f32(p(xr), p(geo.idx), p(geo.wgt), p(y), p(arg), B, H * W, po, C, st),
+                   "eml_sphere_max_pool_fwd_f32")
+        ctx.geo, ctx.shape = geo, (B, C, H, W)
+        y = y.permute(0, 3, 1, 2)
+        if arg is None:
+            return y, None
+        ctx.save_for_backward(arg)
+        arg = arg.permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, _gidx):
+        from .. import _lib
+        L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
+        (arg,) = ctx.saved_tensors
+        geo, (B, C, H, W) = ctx.geo, ctx.shape
+        gyr = _aligned16(gy.permute(0, 2, 3, 1).contiguous())
+        gxr = torch.empty(B, H, W, C, dtype=torch.float32, device=gy.device)      # the kernel writes every element
+        _lib.check(L.eml_sphere_max_pool_bwd_f32(p(gyr), p(arg), p(geo.csr_ptr), p(geo.csr_src), p(geo.csr_w), p(gxr), B, H * W,
+                                                 geo.ho * geo.wo, C, st), "eml_sphere_max_pool_bwd_f32")
+        return gxr.permute(0, 3, 1, 2), None, None
+
+
+def _aligned16(t):
+    """The pool kernels move 16 bytes per lane when C % 4 == 0: a contiguous tensor that starts inside a storage (a slice) is
+    copied to a start of its own."""
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def sphere_max_pool(x, stride=1, return_indices=False):
+    """``max_pool2d(grid_sample(x, grid(H, W, stride)), 3, 3)`` on the MI355X (the reference's ``SphereMaxPool2D.forward``):
+    ``x`` (B, C, H, W) f32 -> channels-last (B, C, ceil(H / stride), ceil(W / stride)); an input in ``torch.channels_last`` is
+    used in place.  The first maximal tap wins and a NaN tap propagates, as in ``max_pool2d``.  ``return_indices``: also the
+    uint8 (B, C, H', W') winning taps ``a*3 + b`` (not differentiable).  Once differentiable; the geometry is the table a
+    SphereConv2D of the same (H, W, stride) uses."""
+    keep = bool(return_indices) or (torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad)
+    y, arg = _SphereMaxPoolFn.apply(x, int(stride), keep)
+    return (y, arg) if return_indices else y
+
+
 def _rows_view(t):
     """(B,C,H,W) tensor in channels-last memory -> (its (B*H*W, C) row-major alias, row stride)."""
     b, c, h, w = t.shape
@@ -1233,3 +1294,25 @@ class SphereConv2D(nn.Module):
         if residual is None and act_slope == 1.0:
             return sphere_conv(x, self.weight, self.bias, self.stride)
         return sphere_conv(x, self.weight, self.bias, self.stride, residual, act_slope)
+
+
+class SphereMaxPool2D(nn.Module):
+    """3x3 spherical max pooling with the reference's signature (``sphere_cnn.py:127-150``): no parameters, no buffers.  Runs
+    on the MI355X only (``sphere_max_pool`` above)."""
+
+    def __init__(self, stride=1, mode="bilinear"):
+        super().__init__()
+        if mode != "bilinear":
+            # the reference's grid puts the centre tap and every row- or column-aligned tap EXACTLY half-way between two texels
+            # (pixel c -> 2c/W - 1 -> c - 0.5 under align_corners=False), so nearest rounding is decided by the last bit of a
+            # float32 coordinate: the same input pooled in f32 and in f64 differs by O(1) (INTEGRATION.md 2.6)
+            why = (": on this grid the taps sample exactly half-way between texels, where nearest rounding is decided by the "
+                   "last bit of a float32 coordinate, not by the operator") if mode == "nearest" else ""
+            raise NotImplementedError("SphereMaxPool2D implements the reference's bilinear mode, not %r%s" % (mode, why))
+        self.stride, self.mode = stride, mode
+
+    def forward(self, x):
+        return sphere_max_pool(x, self.stride)
+
+    def extra_repr(self):
+        return "stride=%d" % self.stride

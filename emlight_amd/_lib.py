@@ -251,6 +251,9 @@ EXT_SIGNATURES = {
     "eml_sinkhorn_fwd_cost_f32": (_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_double, ctypes.c_double, _int,
                                          ctypes.c_double, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _int,
                                          _int, _int, ctypes.c_double, _f32p, ctypes.c_long, _stream]),
+    # SphereMaxPool2D: max over the 9 bilinear taps with the winning tap as uint8; its gather backward over the CSR transpose
+    "eml_sphere_max_pool_fwd_f32": (_int, [_f32p, _i32p, _f32p, _f32p, ctypes.c_void_p, _int, _int, _int, _int, _stream]),
+    "eml_sphere_max_pool_bwd_f32": (_int, [_f32p, ctypes.c_void_p, _i32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),
 }
 
 _lock = threading.Lock()

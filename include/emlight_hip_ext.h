@@ -93,6 +93,29 @@ int eml_sinkhorn_fwd_cost_f32(const float* x, const float* y, const float* M, co
                               float* diameter_out, float* loss, float* gx, float* gy, float* work, int B, int N,
                               int D, int flags, double rho, float* lam_out, long cost_stride, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- SphereMaxPool2D
+ * spherenet/sphere_cnn.py:127-150 (`SphereMaxPool2D.forward`: grid_sample, then max_pool2d(3, 3)) in one pass over the tap
+ * table of eml_sphere_tap_table_f32.  x (B*n_src, C) f32 pixel-major -> y (B*n_dst, C) f32:
+ *   v_t = sum_k wgt[p*9 + t][k] * x[b][idx[p*9 + t][k]][c]   (corners in grid_sampler_2d's order; an index < 0 adds +0)
+ *   y[b][p][c] = max_t v_t,   arg[b][p][c] = the winning tap t = a*3 + b (row-major in the 3x3 window)
+ * max_pool2d's rule: tap t replaces the running maximum when v_t > max or v_t is NaN.  So the first maximal tap wins, a NaN
+ * wins over every number and propagates, and of several NaN taps the last is recorded.
+ * arg: (B*n_dst, C) uint8, or NULL when nobody needs the indices.  An index >= n_src is treated like one < 0.
+ * Limits: B >= 0 (B == 0 returns 0 without a launch); C, n_src, n_dst >= 1; B * n_src, B * n_dst, 9 * n_dst < 2^31 (rows
+ * are 32-bit, element offsets 64-bit); x and y 16-byte aligned when C % 4 == 0.  EML_EINVAL otherwise, nothing enqueued. */
+int eml_sphere_max_pool_fwd_f32(const float* x, const int* idx, const float* wgt, float* y, unsigned char* arg, int B,
+                                int n_src, int n_dst, int C, eml_stream_t stream);
+
+/* spherenet/sphere_cnn.py:127-150, the gradient of the above with respect to x (autograd's max_pool2d backward followed by
+ * grid_sampler's backward), as a gather over the CSR transpose of the tap table (csr_ptr (n_src + 1), csr_src, csr_w: entry
+ * e of row q has output pixel csr_src[e] / 9, tap csr_src[e] % 9 and bilinear weight csr_w[e]):
+ *   gx[b][q][c] = sum over e in row q with arg[b][csr_src[e] / 9][c] == csr_src[e] % 9 of csr_w[e] * gy[b][csr_src[e] / 9][c]
+ * summed in CSR order with one fmaf per term; terms of taps that lost are skipped, not multiplied by 0.  No atomics: run-to-run
+ * exact.  Every element of gx (B*n_src, C) is written; a pixel with an empty row gets 0.  Entries with csr_src / 9 >= n_dst
+ * are skipped.  Limits and alignment as for the forward; gy, gx 16-byte and arg 4-byte aligned when C % 4 == 0. */
+int eml_sphere_max_pool_bwd_f32(const float* gy, const unsigned char* arg, const int* csr_ptr, const int* csr_src,
+                                const float* csr_w, float* gx, int B, int n_src, int n_dst, int C, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
