@@ -112,8 +112,8 @@ def resize_bilinear(x, size, alpha=None, clip=False):
 def resize_exr(img, res_x=512, res_y=512, theta=0.0, phi=0.0, move=0.0):
     """The reference's ``resize_exr(img, res_x, res_y)`` (``GenProjector/util.py:279-343``) on device tensors, one image
     ``(H, W, 3)`` or a batch: ``res_x`` is the number of ROWS of the result and ``res_y`` its columns, as there; the three
-    constants of ``util.py:281`` are keywords (degrees, degrees, sphere radii; numbers or ``(B,)`` device tensors).  See
-    ``PanoramaHandler.warp_panorama``."""
+    constants of ``util.py:281`` are keywords (degrees, degrees, sphere radii; numbers or ``(B,)`` device tensors).  Differentiable
+    (once) in the image and in parameter tensors that require grad.  See ``PanoramaHandler.warp_panorama``."""
     return PanoramaHandler.warp_panorama(img, (int(res_y), int(res_x)), theta=theta, phi=phi, move=move)
 
 

@@ -4,7 +4,7 @@
 ``sphere_points`` (``util.py:286-299``) is the small host helper the kept entry points need.
 ``PanoramaHandler`` (``util.py:69-185``: crop, rotate, resize) and ``TonemapHDR`` (``util.py:36-66``) run on device
 tensors, batched (csrc/pano_prep.hip); ``PanoramaHandler.warp_panorama`` is the panorama warp of ``GenProjector/util.py:279-343``
-(csrc/pano_warp.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
+(csrc/pano_warp.hip, gradients: csrc/pano_warp_bwd.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
 EXR/vtk/cv2 I/O is out of scope.
 """
 import functools
@@ -150,6 +150,82 @@ def _per_sample(value, B, name):
     return float(value), None
 
 
+def _warp_forward(x, params, vals, hw, return_coords):
+    """The one ``eml_pano_warp_f32`` call of ``PanoramaHandler.warp_panorama``: ``x`` (B, H, W, 3), ``params`` (B, 3) float64 or
+    ``None`` (then ``vals`` = (theta, phi, move) hold for the batch) -> ``(out, coords or None)``."""
+    B, H, W, _ = x.shape
+    h, w = hw
+    n_sets = B if params is not None else 1
+    out = torch.empty(B, h, w, 3, dtype=torch.float32, device=x.device)
+    coords = torch.empty(n_sets, h, w, 2, dtype=torch.float64, device=x.device) if return_coords else None
+    if B > 0:       # an empty batch has no storage to point at
+        _lib.check(_lib.lib().eml_pano_warp_f32(_lib.ptr(x), B, H, W, h, w, vals[0], vals[1], vals[2],
+                                                _lib.ptr(params), _lib.ptr(out), _lib.ptr(coords), _lib.current_stream()),
+                   "eml_pano_warp_f32")
+    return out, coords
+
+
+def warp_panorama_bwd_raw(grad_out, pano, pano_hw, theta=0.0, phi=0.0, move=0.0, params=None, want_dpano=True,
+                          want_dparams=True):
+    """``eml_pano_warp_bwd_f32`` (no autograd): the gradients of the warp for ``grad_out`` (B, h, w, 3) float32.  ``pano``
+    (B, H, W, 3) float32 is read for ``dparams`` only and may be ``None`` otherwise; ``pano_hw`` = (H, W).  ``params``: the
+    (B, 3) float64 device array of per-sample (theta, phi, move), or ``None`` for the three by-value numbers.  Returns
+    ``(dpano (B, H, W, 3) float32 or None, dparams (B, 3) float64 or None)``; ``dparams`` has one row per sample also with
+    by-value parameters."""
+    g = _lib.require_gpu_tensor(grad_out, "grad_out")
+    if g.dim() != 4 or g.shape[-1] != 3:
+        raise ValueError("grad_out: expected (B, h, w, 3), got %s" % (tuple(g.shape),))
+    B, h, w, _ = g.shape
+    H, W = int(pano_hw[0]), int(pano_hw[1])
+    if not (want_dpano or want_dparams):
+        raise ValueError("warp_panorama_bwd_raw: no gradient requested")
+    x = None
+    if want_dparams:
+        x = _lib.require_gpu_tensor(pano, "pano")
+        if x.shape != (B, H, W, 3):
+            raise ValueError("pano: expected %s, got %s" % ((B, H, W, 3), tuple(x.shape)))
+    if params is not None:
+        params = _lib.require_gpu_tensor(params, "params", torch.float64)
+        if params.shape != (B, 3):
+            raise ValueError("params: expected (%d, 3), got %s" % (B, tuple(params.shape)))
+    dpano = torch.empty(B, H, W, 3, dtype=torch.float32, device=g.device) if want_dpano else None
+    dparams = torch.empty(B, 3, dtype=torch.float64, device=g.device) if want_dparams else None
+    if B > 0:
+        L = _lib.lib()
+        n = L.eml_pano_warp_bwd_work_floats(B, H, W, h, w, 1 if want_dpano else 0, 1 if want_dparams else 0)
+        work = torch.empty(max(1, (n + 1) // 2), dtype=torch.float64, device=g.device)      # float64: 8-byte aligned
+        _lib.check(L.eml_pano_warp_bwd_f32(_lib.ptr(g), _lib.ptr(x), B, H, W, h, w, float(theta), float(phi), float(move),
+                                           _lib.ptr(params), _lib.ptr(dpano), _lib.ptr(dparams), _lib.ptr(work),
+                                           _lib.current_stream()), "eml_pano_warp_bwd_f32")
+    return dpano, dparams
+
+
+class _WarpPanorama(torch.autograd.Function):
+    """``warp_panorama`` for autograd: inputs ``x`` (B, H, W, 3) and the packed ``params`` (B, 3) float64 or ``None``.  The
+    packing (``torch.stack`` of the ``(B,)`` tensors cast to float64) is autograd's, so each parameter tensor receives its
+    column in its own dtype and Python numbers get nothing."""
+
+    @staticmethod
+    def forward(ctx, x, params, vals, hw, return_coords):
+        out, coords = _warp_forward(x, params, vals, hw, return_coords)
+        need_params = params is not None and ctx.needs_input_grad[1]
+        ctx.save_for_backward(x if need_params else None, params)    # the panorama enters d / d(theta, phi, move) only
+        ctx.pano_hw, ctx.vals = (x.shape[1], x.shape[2]), vals
+        if not return_coords:
+            return out
+        ctx.mark_non_differentiable(coords)
+        return out, coords
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, *_):
+        x, params = ctx.saved_tensors
+        need_x, need_params = ctx.needs_input_grad[0], x is not None
+        dpano, dparams = warp_panorama_bwd_raw(gout, x, ctx.pano_hw, *ctx.vals, params=params, want_dpano=need_x,
+                                               want_dparams=need_params)
+        return dpano, dparams, None, None, None
+
+
 def parse_aspect_ratio(text):
     """``"a:b"`` -> a / b (``util.py:152-153``); anything else is a ``ValueError``."""
     try:
@@ -271,7 +347,12 @@ class PanoramaHandler(object):
         synchronisation) and every sample is evaluated on its own.  By-value parameters that are not finite raise
         ``ValueError``; a per-sample value that gives no finite position (NaN; ``|move| == 1`` at the one direction that
         falls on the new viewpoint) gives NaN pixels.  ``return_coords``: also the float64 source positions ``(row, col)``,
-        ``(n, h, w, 2)`` with ``n = B`` for per-sample parameters, else 1 (``(h, w, 2)`` for a single image)."""
+        ``(n, h, w, 2)`` with ``n = B`` for per-sample parameters, else 1 (``(h, w, 2)`` for a single image); they carry no
+        gradient.  With grad mode on and a panorama or a parameter tensor that requires grad, the result is differentiable
+        (once; ``eml_pano_warp_bwd_f32``): the panorama's gradient has the panorama's shape, each ``(B,)``
+        parameter tensor receives its gradient in its own dtype, Python numbers get none; a position that is an integer
+        differentiates in its right-hand cell, a pixel within 0.06 degrees of the source's pole adds nothing to the parameters'
+        gradients.  Otherwise the call is the one forward launch, bit for bit."""
         x, single = PanoramaHandler._batched(hdr_img, "hdr_img")
         B, H, W, _ = x.shape
         if new_shape is None:
@@ -292,13 +373,12 @@ class PanoramaHandler(object):
             vals = [(0.0, None)] * 3
         elif not all(np.isfinite(v) for v, _ in vals):
             raise ValueError("warp_panorama: theta, phi and move must be finite, got %r" % ([v for v, _ in vals],))
-        n_sets = B if params is not None else 1
-        out = torch.empty(B, h, w, 3, dtype=torch.float32, device=x.device)
-        coords = torch.empty(n_sets, h, w, 2, dtype=torch.float64, device=x.device) if return_coords else None
-        if B > 0:       # an empty batch has no storage to point at
-            _lib.check(_lib.lib().eml_pano_warp_f32(_lib.ptr(x), B, H, W, h, w, vals[0][0], vals[1][0], vals[2][0],
-                                                    _lib.ptr(params), _lib.ptr(out), _lib.ptr(coords), _lib.current_stream()),
-                       "eml_pano_warp_f32")
+        vals = tuple(v for v, _ in vals)
+        if torch.is_grad_enabled() and (x.requires_grad or (params is not None and params.requires_grad)):
+            res = _WarpPanorama.apply(x, params, vals, (h, w), bool(return_coords))
+            out, coords = res if return_coords else (res, None)
+        else:
+            out, coords = _warp_forward(x, params, vals, (h, w), return_coords)
         if single:
             out = out[0]
             coords = coords[0] if return_coords else None

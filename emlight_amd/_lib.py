@@ -241,6 +241,10 @@ EXT_SIGNATURES = {
     # panorama warp (resize_exr): rotate, translate, resample with wrap-around
     "eml_pano_warp_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p,
                                  _f32p, _f64p, _stream]),
+    # its gradients: the adjoint for the panorama (64-bit fixed-point scatter) and d / d(theta, phi, move)
+    "eml_pano_warp_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int, _int, _int]),
+    "eml_pano_warp_bwd_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, _f64p, _f32p, _f64p, _f32p, _stream]),
     # render loss: the adjoint of the sphere renders (gradient with respect to the panorama) and the mirror's tap list
     "eml_sphere_render_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int]),
     "eml_sphere_render_bwd_f32": (_int, [_f32p, _int, _int, _int, _int, ctypes.c_double, _int, ctypes.c_double, _i32p, _i32p,

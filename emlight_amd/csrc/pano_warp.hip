@@ -24,61 +24,13 @@
 // operations, the same with by-value and with per-sample parameters, so an image gives the same bits in any batch.
 #include "eml_common.h"
 #include "../../include/emlight_hip_ext.h"
+#include "pano_warp_pos.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr double kSnap = 1.0 / (double)(1 << 28);   // px
-constexpr int kRun = 4;                              // images per evaluated position with by-value parameters
-
-__device__ __forceinline__ double snap_px(double x) {
-  const double n = rint(x);
-  return fabs(x - n) < kSnap ? n : x;
-}
-
-// (row, col) of output pixel (i, j); false (and NaNs) where the position is not finite: |v| == 0, possible only at
-// |move| == 1, a NaN or infinite parameter, an overflow of move * m.
-__device__ __forceinline__ bool warp_position(int i, int j, int h, int w, int H, int W, double theta_deg, double phi_deg,
-                                              double move, double& row, double& col) {
-#pragma clang fp contract(off)
-  const double lat = (double)i * kPi / (double)h - kPi / 2.0, lon = (double)j * (2.0 * kPi) / (double)w;
-  const double clat = cos(lat);
-  const double d0 = sin(lat), d1 = sin(lon) * clat, d2 = -cos(lon) * clat;
-  const double theta = theta_deg / 180.0 * kPi, phi = phi_deg / 180.0 * kPi;
-  const double ct = cos(theta), st = sin(theta), c = cos(phi), s = -sin(phi), k = 1.0 - c;
-  // Rt d and Rt (0, 0, -1)
-  const double e0 = d0, e1 = ct * d1 - st * d2, e2 = st * d1 + ct * d2;
-  const double n0 = 0.0, n1 = st, n2 = -ct;
-  // Rp, axis (0, ay, az)
-  const double ay = ct, az = st;
-  const double r00 = c, r01 = -az * s, r02 = ay * s;
-  const double r10 = az * s, r11 = c + ay * ay * k, r12 = ay * az * k;
-  const double r20 = -ay * s, r21 = az * ay * k, r22 = c + az * az * k;
-  const double m0 = r00 * n0 + r01 * n1 + r02 * n2, m1 = r10 * n0 + r11 * n1 + r12 * n2, m2 = r20 * n0 + r21 * n1 + r22 * n2;
-  const double v0 = (r00 * e0 + r01 * e1 + r02 * e2) + move * m0;
-  const double v1 = (r10 * e0 + r11 * e1 + r12 * e2) + move * m1;
-  const double v2 = (r20 * e0 + r21 * e1 + r22 * e2) + move * m2;
-  const double len = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-  row = col = __builtin_nan("");
-  if (!(len > 0.0) || !isfinite(len)) return false;
-  const double s0 = fmin(fmax(v0 / len, -1.0), 1.0), s1 = v1 / len, s2 = v2 / len;
-  double az_s = atan2(s1, -s2);
-  if (az_s < 0.0) az_s += 2.0 * kPi;      // numpy's `% (2 pi)` on [-pi, pi]; -tiny + 2 pi rounds to 2 pi: col == W
-  if (az_s == 0.0) az_s = 0.0;            // -0 -> +0
-  const double r = snap_px((asin(s0) + kPi / 2.0) / kPi * (double)H);
-  const double q = snap_px(az_s / (2.0 * kPi) * (double)W);
-  if (!isfinite(r) || !isfinite(q)) return false;
-  row = r;
-  col = q;
-  return true;
-}
-
-__device__ __forceinline__ int wrap_index(long long k, int n) {
-  const int m = (int)(k % (long long)n);
-  return m < 0 ? m + n : m;
-}
+using namespace eml::warp;   // warp_position, wrap_index, kRun: pano_warp_pos.h, shared with pano_warp_bwd.hip
 
 // grid (pixel tiles, runs): blockIdx.y covers images [y * per, (y + 1) * per); with params (one (theta, phi, move) per
 // sample) per == 1.  out (B, h, w, 3); coords (n_sets, h, w, 2) or null, n_sets = B with params, else 1 (run 0 writes it).

@@ -41,6 +41,40 @@ extern "C" {
 int eml_pano_warp_f32(const float* pano, int B, int H, int W, int h, int w, double theta_deg, double phi_deg, double move,
                       const double* params_dev, float* out, double* coords, eml_stream_t stream);
 
+/* GenProjector/util.py:279-343, the gradients of eml_pano_warp_f32 (the reference has none).  Per output
+ * pixel p = (i, j) of sample b the forward has a source position (row, col) in f64, snapped to an integer when closer than
+ * 2^-28 px; taps i0 = floor(row) mod H, i1 = i0 + 1 mod H, j0, j1 likewise; fractions yd, xd; and
+ *   out = w00 I00 + w01 I01 + w10 I10 + w11 I11,  w00 = (1-yd)(1-xd), w01 = (1-yd) xd, w10 = yd (1-xd), w11 = yd xd.
+ * A pixel whose position is not finite (NaN in the forward) contributes nothing to either gradient.
+ * grad_out (B,h,w,3) f32 = g.
+ * dpano (B,H,W,3) f32 or NULL, every element written:
+ *   dpano[b,t,ch] = sum over (p, k) whose tap k lands on texel t of w_k(b,p) g[b,p,ch]
+ * with the forward's own f64 weights, made from the snapped position.  Each product is formed in f64, rounded once to a
+ * multiple of u_b = 2^(e_b - 61), where 2^e_b is the power of two above S_b = sum |g[b]| (taken in f64 in a fixed order by a
+ * first pass), and added in 64-bit integers; the integer sum is exact and order-independent, and is rounded to f32 once.
+ * |error before that rounding| <= n 2^-61 S_b for a texel that n taps land on.  Two taps of one pixel that name the same
+ * texel (H == 1 or W == 1) both add; a texel that nothing lands on is exactly 0.
+ * dparams (B,3) f64 or NULL, order theta_deg, phi_deg, move, one row per sample also with by-value parameters:
+ *   dparams[b,q] = sum_p sum_ch g[b,p,ch] (dOut/dRow dRow/dq + dOut/dCol dCol/dq)
+ *   dOut/dRow = (1-xd)(I10-I00) + xd (I11-I01),  dOut/dCol = (1-yd)(I01-I00) + yd (I11-I10)
+ * in the cell the forward used (at an integer position the right-hand cell, grid_sample's convention), in f64 from the f32
+ * texels.  dRow/dq, dCol/dq: the derivative of the unsnapped position formula (degree-to-radian factor, both rotations,
+ * move * m, the normalisation, asin, atan2; the clamp of s0, the `mod 2 pi` and the snap are the identity), forward mode in
+ * f64.  Pole rule: a pixel with s1^2 + s2^2 < 2^-20 (1 - s0^2 formed as that sum) contributes 0 to dparams; its
+ * contribution to dpano is unaffected.  The sum over pixels is a fixed-order f64 reduction: a tree inside each 256-pixel
+ * tile, the tiles' partials into `work`, then one fixed-order pass per sample.
+ * Run-to-run exact; a sample's gradients have the same bits in any batch and with by-value and per-sample parameters.  Only
+ * enqueues: no host synchronisation, no host work that depends on the parameters.  Non-finite values in grad_out leave that
+ * sample's gradients unspecified; tap indices never depend on grad_out and are reduced modulo the size.
+ * pano may be NULL when dparams is NULL.  work: eml_pano_warp_bwd_work_floats(...) floats (0 when a size is refused, B == 0
+ * or nothing is wanted), 8-byte aligned.  Limits as eml_pano_warp_f32.  EML_EINVAL with nothing enqueued: a NULL grad_out;
+ * both outputs NULL; dparams without pano; bad sizes; non-finite by-value parameters (params_dev == NULL); a NULL or
+ * misaligned work with B > 0.  B == 0 returns 0. */
+size_t eml_pano_warp_bwd_work_floats(int B, int H, int W, int h, int w, int want_dpano, int want_dparams);
+int eml_pano_warp_bwd_f32(const float* grad_out, const float* pano, int B, int H, int W, int h, int w, double theta_deg,
+                          double phi_deg, double move, const double* params_dev, float* dpano, double* dparams, float* work,
+                          eml_stream_t stream);
+
 /* ---------------------------------------------------------------- render loss: the adjoint of the sphere renders
  * The reference tree has no such code; DESIGN.md section 15 is the definition (as for eml_sphere_render_f32, whose
  * geometry, materials mask, material order and limits these share).  eml_sphere_render_f32 is linear in the panorama:
