@@ -403,7 +403,7 @@ def _sphere_conv_backward(plan, geo, shape, needs, gy, saved, has_bias, slope=1.
     """Backward of a SphereConv layer that ran under ``plan`` (``_conv_plan``) -> (dx, dweight, dbias, dresidual).  ``shape``:
     (B, C, H, W, O); ``needs``: a ``_Needs``; ``saved``: (the im2col operand where ``plan.keep`` else the pixel-major input, the
     weight[, the output where slope != 1]).  Shared with the one-launch SPADE, whose backward feeds it the (dgamma | dbeta)
-    tensor."""
+    tensor -- and no weight (None) where the guide map takes no gradient: only the input gradient reads it."""
     from .. import _lib
     L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
     xr, weight = saved[:2]
@@ -436,14 +436,23 @@ def _sphere_conv_backward(plan, geo, shape, needs, gy, saved, has_bias, slope=1.
         _lib.check(L.eml_sphere_col2im_f32(p(da9), p(geo.csr_ptr), p(geo.csr_src), p(geo.csr_w), p(gxr), B, H * W, po, C, st),
                    "eml_sphere_col2im_f32")
         gx = gxr.permute(0, 3, 1, 2)
+    # ... and the bias gradient on its own (a frozen weight): the bias column of the same product, the bits the weight gradient's
+    # kernel leaves (eml_sphere_conv_small_dbias_f32) -- one read of (dY, Y), no activation-backward pass and column sum
+    small_b = plan.fwd == "small" and has_bias and needs.bias and not small_w
+    if small_b:
+        part = new(L.eml_sphere_conv_small_wgrad_partial_floats(B, po, C, O))
+        gb = new(O)
+        _lib.check(L.eml_sphere_conv_small_dbias_f32(p(gyr), p(y), slope, p(part), p(gb), B, po, C, O, st),
+                   "eml_sphere_conv_small_dbias_f32")
+        del part
     need_masked = ((needs.x and not small_x) or needs.residual
-                   or (not small_w and (needs.weight or (has_bias and needs.bias))))
+                   or (not small_w and (needs.weight or (has_bias and needs.bias and not small_b))))
     if y is not None and need_masked:
         gyr = (torch.ops.aten.threshold_backward(gyr, y, 0.0) if slope == 0.0
                else torch.ops.aten.leaky_relu_backward(gyr, y, slope, True))
     if needs.residual:
         gres = gyr.view(B, geo.ho, geo.wo, O).permute(0, 3, 1, 2)
-    if has_bias and needs.bias and not small_w:
+    if has_bias and needs.bias and not small_w and not small_b:
         # the SPADE modulation's backward leaves the column sums of the dgb it produced on the tensor (f64-accumulated)
         # -- valid only for the very tensor it was computed from: same storage, not written since (autograd accumulates
         # IN PLACE into a gradient that has a second consumer; a hook may hand over a different tensor): ADVICE round 3
@@ -554,7 +563,7 @@ def _sphere_conv_backward(plan, geo, shape, needs, gy, saved, has_bias, slope=1.
                 _lib.check(L.eml_sphere_col2im_f32(p(da9), p(geo.csr_ptr), p(geo.csr_src), p(geo.csr_w), p(gxr), B,
                                                    H * W, po, C, st), "eml_sphere_col2im_f32")
         gx = gxr.permute(0, 3, 1, 2)
-    if gw is not None and weight.is_leaf:
+    if gw is not None and weight is not None and weight.is_leaf:
         # data-parallel runs, a weight that is a parameter itself (SPADE's heads, conv_img, the first discriminator layer):
         # the re-layout to the parameter's own order -- which autograd would make anyway when it adopts a permuted view --
         # lands in the parameter's place in its gradient bucket (_dist.grad_slot: nothing to pack)
@@ -829,7 +838,9 @@ class _SpadeNormModulateFn(torch.autograd.Function):
         _lib.check(L.eml_spade_norm_modulate_bwd_cols_f32(p(gy), p(x), p(gb), p(dxn), p(dgb), B, H, W, C, int(ctx.up2), ctx.slope,
                                                           p(mean), p(istd), p(partials), grid, st),
                    "eml_spade_norm_modulate_bwd_cols_f32")
-        dx = _spade_bn_backward_tail(partials, x, dxn, dgb, mean, istd, (B, H, W, C), ctx.up2, ctx.training)
+        # (a frozen or detached x -- only the heads or the guide map train: no BatchNorm backward pass)
+        dx = _spade_bn_backward_tail(partials, x, dxn, dgb, mean, istd, (B, H, W, C), ctx.up2, ctx.training,
+                                     need_dx=ctx.needs_input_grad[0])
         return dx, dgb, None, None, None, None, None
 
 

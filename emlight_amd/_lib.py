@@ -258,6 +258,8 @@ EXT_SIGNATURES = {
     # SphereMaxPool2D: max over the 9 bilinear taps with the winning tap as uint8; its gather backward over the CSR transpose
     "eml_sphere_max_pool_fwd_f32": (_int, [_f32p, _i32p, _f32p, _f32p, ctypes.c_void_p, _int, _int, _int, _int, _stream]),
     "eml_sphere_max_pool_bwd_f32": (_int, [_f32p, ctypes.c_void_p, _i32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),
+    # the 3-channel input layers' bias gradient without their weight gradient: the bias column of the same product
+    "eml_sphere_conv_small_dbias_f32": (_int, [_f32p, _f32p, ctypes.c_float, _f32p, _f32p, _int, _int, _int, _int, _stream]),
 }
 
 _lock = threading.Lock()

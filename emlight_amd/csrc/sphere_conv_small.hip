@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "eml_common.h"
+#include "../../include/emlight_hip_ext.h"
 
 namespace {
 
@@ -439,6 +440,100 @@ void launch_small_wgrad(const float* X, const int* idx, const float* wgt, const 
   hipLaunchKernelGGL(small_wgrad_reduce_kernel, dim3((O * KP + 15) / 16), dim3(256), 0, st, partial, grid, O, K, KP, dW2, db);
 }
 
+// The bias gradient ALONE (a frozen weight): column K of the weight gradient's product, bit for bit.  An MFMA output column
+// depends on its own column of B only, so the same MFMA sequence on the same A operands with B = the ones column -- the same
+// pixel <-> (wave, step, k-slot) assignment (steps past the end add zeros, two steps per turn as above), the same sum of the
+// four waves through LDS, the same grid and the same fixed-order reduction of the workgroup partials -- leaves in column K what
+// sphere_conv_small_wgrad_kernel leaves there, without the gather.  partial[blockIdx.x][O].
+template <int CIN, int O>
+__global__ __launch_bounds__(256, 2) void sphere_conv_small_dbias_kernel(const float* __restrict__ dY, const float* __restrict__ Yact,
+                                                                      float* __restrict__ partial, int M, float slope) {
+  constexpr int K = 9 * CIN, KR = K % 16, NG = O / 64, U = 2;   // column K = column KR of its 16-wide tile
+  __shared__ float smem[3 * O];                                 // wave partials of waves 1..3
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, wv = threadIdx.x >> 6;
+  const int wave = blockIdx.x * 4 + wv, nwaves = gridDim.x * 4;
+  f32x4 acc[NG][4];   // [64-channel group][component t of the float4]: row r <-> channel 64G + 4r + t
+#pragma unroll
+  for (int G = 0; G < NG; ++G)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[G][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nsteps = (M + 4 * U - 1) / (4 * U);
+  auto run_step = [&](int st) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int m = (st * U + u) * 4 + g;
+      const bool ok = st < nsteps && m < M;
+      const size_t row = (size_t)(ok ? m : 0) * O;     // every load unconditional from a clamped pixel
+      const float bv = ok && r == KR ? 1.f : 0.f;
+#pragma unroll
+      for (int G = 0; G < NG; ++G) {
+        f32x4 q = *reinterpret_cast<const f32x4*>(dY + row + 64 * G + 4 * r);
+        if (Yact) {
+          const f32x4 yq = *reinterpret_cast<const f32x4*>(Yact + row + 64 * G + 4 * r);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) q[e] = yq[e] > 0.f ? q[e] : q[e] * slope;
+        }
+        if (!ok) q = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc[G][0] = mfma16(q[0], bv, acc[G][0]);
+        acc[G][1] = mfma16(q[1], bv, acc[G][1]);
+        acc[G][2] = mfma16(q[2], bv, acc[G][2]);
+        acc[G][3] = mfma16(q[3], bv, acc[G][3]);
+      }
+    }
+  };
+  for (int st = wave; st < nsteps; st += 2 * nwaves) {
+    run_step(st);
+    run_step(st + nwaves);
+  }
+  // D element i of tile (G, t): row 4g + i <-> channel 64G + 4(4g + i) + t, column r; the bias gradient sits in column KR
+  if (wv > 0 && r == KR) {
+#pragma unroll
+    for (int G = 0; G < NG; ++G)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) smem[(wv - 1) * O + 64 * G + 4 * (4 * g + i) + t] = acc[G][t][i];
+  }
+  __syncthreads();
+  if (wv == 0 && r == KR) {
+    float* out = partial + (size_t)blockIdx.x * O;
+#pragma unroll
+    for (int G = 0; G < NG; ++G)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int c = 64 * G + 4 * (4 * g + i) + t;
+          out[c] = ((acc[G][t][i] + smem[c]) + smem[O + c]) + smem[2 * O + c];
+        }
+  }
+}
+
+// db[o] = the sum of the S workgroup partials in small_wgrad_reduce_kernel's order: 16 strided running sums, then their sum
+__global__ __launch_bounds__(256) void small_dbias_reduce_kernel(const float* __restrict__ partial, int S, int O,
+                                                                 float* __restrict__ db) {
+  __shared__ float red[16][17];
+  const int el = threadIdx.x & 15, zl = threadIdx.x >> 4;
+  const int o = blockIdx.x * 16 + el;
+  float s = 0.f;
+  if (o < O)
+    for (int z = zl; z < S; z += 16) s += partial[(size_t)z * O + o];
+  red[zl][el] = s;
+  __syncthreads();
+  if (zl == 0 && o < O) {
+    float tot = 0.f;
+#pragma unroll
+    for (int z = 0; z < 16; ++z) tot += red[z][el];
+    db[o] = tot;
+  }
+}
+
+template <int CIN, int O>
+void launch_small_dbias(const float* dY, const float* Yact, float* partial, float* db, int M, float slope, int grid, hipStream_t st) {
+  hipLaunchKernelGGL((sphere_conv_small_dbias_kernel<CIN, O>), dim3(grid), dim3(256), 0, st, dY, Yact, partial, M, slope);
+  hipLaunchKernelGGL(small_dbias_reduce_kernel, dim3((O + 15) / 16), dim3(256), 0, st, partial, grid, O, db);
+}
+
 int small_kp(int C) { return 16 * ((9 * C + 1 + 15) / 16); }
 bool small_supported(int C, int O) { return C == 3 && (O == 64 || O == 128); }
 // one workgroup per 128 pixels up to the persistent grid (round 6; it was one per 1024: the 1 K pixels of a 4 x 8 layer ran on
@@ -499,6 +594,28 @@ extern "C" int eml_sphere_conv_small_wgrad_f32(const float* X, const int* idx, c
   if (O == 128) launch_small_wgrad<3, 128>(X, idx, wgt, dY, ya, partial, dW2, db, (int)M, HW, Po, act_slope, grid, st);
   else launch_small_wgrad<3, 64>(X, idx, wgt, dY, ya, partial, dW2, db, (int)M, HW, Po, act_slope, grid, st);
   return eml::check_launch("eml_sphere_conv_small_wgrad_f32");
+}
+
+extern "C" int eml_sphere_conv_small_dbias_f32(const float* dY, const float* Yact, float act_slope, float* partial, float* db,
+                                               int B, int Po, int C, int O, eml_stream_t stream) {
+  if (!dY || !partial || !db || B < 0 || Po < 1)
+    return eml::fail(EML_EINVAL, "eml_sphere_conv_small_dbias_f32: null pointer or empty shape");
+  if (!small_supported(C, O))
+    return eml::fail(EML_EINVAL, "eml_sphere_conv_small_dbias_f32: (C, O) = (%d, %d) not in {(3, 64), (3, 128)}", C, O);
+  if (!(act_slope >= 0.f && act_slope <= 1.f) || (act_slope != 1.f && !Yact))
+    return eml::fail(EML_EINVAL, "eml_sphere_conv_small_dbias_f32: act_slope %g needs Yact and a slope in [0, 1]", (double)act_slope);
+  const long M = (long)B * Po;
+  if (M > 2147483647L - 16) return eml::fail(EML_EINVAL, "eml_sphere_conv_small_dbias_f32: too many pixels");
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) {
+    (void)hipMemsetAsync(db, 0, (size_t)O * sizeof(float), st);
+    return eml::check_launch("eml_sphere_conv_small_dbias_f32");
+  }
+  const int grid = small_wgrad_grid(M);   // the weight gradient's grid: the partials are its column K
+  const float* ya = act_slope != 1.f ? Yact : nullptr;
+  if (O == 128) launch_small_dbias<3, 128>(dY, ya, partial, db, (int)M, act_slope, grid, st);
+  else launch_small_dbias<3, 64>(dY, ya, partial, db, (int)M, act_slope, grid, st);
+  return eml::check_launch("eml_sphere_conv_small_dbias_f32");
 }
 
 extern "C" int eml_sphere_conv_small_da9_f32(const float* dY, const float* Yact, float act_slope, const float* W2, float* dA9,

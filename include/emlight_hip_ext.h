@@ -150,6 +150,19 @@ int eml_sphere_max_pool_fwd_f32(const float* x, const int* idx, const float* wgt
 int eml_sphere_max_pool_bwd_f32(const float* gy, const unsigned char* arg, const int* csr_ptr, const int* csr_src,
                                 const float* csr_w, float* gx, int B, int n_src, int n_dst, int C, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- SphereConv, 3-channel input layers: the bias gradient alone
+ * spherenet/sphere_cnn.py:111-124 with the ReLU of normalization.py:92-96 folded in: the bias gradient of a 3 -> 64 / 3 -> 128
+ * layer whose weight takes no gradient (eml_sphere_conv_small_wgrad_f32, emlight_hip.h, gives it together with dW2):
+ *   db[o] = sum_m g'[m][o],   g' = dY * (Yact > 0 ? 1 : act_slope),   m < B * Po
+ * one read of (dY, Yact) instead of an activation-backward pass and a column sum.  The result equals the db of
+ * eml_sphere_conv_small_wgrad_f32 on the same (dY, Yact) BIT FOR BIT: the same MFMA sequence on the ones column alone, the
+ * same grid, the same fixed-order sums (no atomics: run-to-run exact).
+ * dY, Yact (B*Po, O) 16-byte aligned; Yact = the forward's output, NULL with act_slope = 1; act_slope in [0, 1]; (C, O) in
+ * {(3, 64), (3, 128)}; partial: eml_sphere_conv_small_wgrad_partial_floats(B, Po, C, O) floats of scratch suffice (one per
+ * workgroup and channel is used).  B == 0 zeroes db.  EML_EINVAL otherwise, nothing enqueued. */
+int eml_sphere_conv_small_dbias_f32(const float* dY, const float* Yact, float act_slope, float* partial, float* db, int B,
+                                    int Po, int C, int O, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
