@@ -260,6 +260,12 @@ EXT_SIGNATURES = {
     "eml_sphere_max_pool_bwd_f32": (_int, [_f32p, ctypes.c_void_p, _i32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _stream]),
     # the 3-channel input layers' bias gradient without their weight gradient: the bias column of the same product
     "eml_sphere_conv_small_dbias_f32": (_int, [_f32p, _f32p, ctypes.c_float, _f32p, _f32p, _int, _int, _int, _int, _stream]),
+    # object insertion: prefiltered environment maps (implicit GEMM; `lobes` is a HOST array of doubles) and G-buffer shading
+    "eml_env_prefilter_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int]),
+    "eml_env_prefilter_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_void_p, _f32p, _f32p, _stream]),
+    "eml_gbuffer_shade_f32": (_int, [_f32p, _int, _f32p, _int, ctypes.c_long, _f32p, _int, ctypes.c_long, _f32p, _f32p, _f32p,
+                                     _f32p, _f32p, _int, _int, _int, ctypes.c_double, ctypes.c_double, _f32p, _f32p, _f32p,
+                                     ctypes.c_double, _f32p, _stream]),
 }
 
 _lock = threading.Lock()

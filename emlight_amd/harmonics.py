@@ -225,7 +225,8 @@ class HarmonicBasis:
                         scale[rows, cols] = np.sqrt(lam[j]) * window[j, l]
             centres = np.concatenate([[[0.0, 0.0, 1.0]], needlets.cubature(jmax)], 0)
             T = self._matrix_at(self._upload(centres)) * self._upload(scale)
-            T[0, 0] = 1.0                                                  # row 0 of the needlet basis is Y_00 itself
+            T[0] = 0.0                                                     # row 0 of the needlet basis is Y_00 itself: set, not
+            T[0, 0] = 1.0                                                  # left to 0 * (whatever the basis kernel wrote there)
             self._to_needlets[jmax] = T
         return self._to_needlets[jmax]
 

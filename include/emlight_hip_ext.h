@@ -163,6 +163,56 @@ int eml_sphere_max_pool_bwd_f32(const float* gy, const unsigned char* arg, const
 int eml_sphere_conv_small_dbias_f32(const float* dY, const float* Yact, float act_slope, float* partial, float* db, int B,
                                     int Po, int C, int O, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- object insertion: prefiltered environment maps
+ * The reference tree has no such code (its README describes the use: a virtual object lit by the predicted panorama);
+ * DESIGN.md section 22 is the definition, and the lobes are section 15's two materials (eml_sphere_render_f32) evaluated at
+ * the texel directions of an output grid instead of at a sphere's normals.  pano (B,3,H,W) f32, W == 2H ->
+ * out (B,L,3,Ho,2Ho) f32, every element written:
+ *   out[b,l,ch,d] = c_l sum_t pano[b,ch,t] k_l(omega_d . omega_t) dOmega_t
+ * with omega, dOmega of the equirectangular grids of heights Ho (d) and H (t) as in section 15.  lobes: HOST array of L
+ * doubles, read before the call returns: a value < 0 is the diffuse lobe (k = max(0, x), c = 1/pi), a value m >= 0 the Phong
+ * lobe (k = max(0, x)^m, c = (m + 1) / 2 pi, 0^0 = 1).  An implicit GEMM on v_mfma_f32_32x32x2_f32 (rows: the 2 Ho^2
+ * directions, k: the texels, columns: the 3B planes); the weights are never stored; two lobes share one read of the
+ * panorama operand, L > 2 takes ceil(L / 2) passes.  No atomics: run-to-run exact.  The split over k is a function of (H, Ho)
+ * alone and is added in split order, so an image's maps have the same bits in any batch; a lobe's arithmetic does not
+ * depend on the lobe it shares a pass with, so its map has the same bits whatever else was asked for and in any position.
+ * work: eml_env_prefilter_work_floats(B, H, W, Ho, L) floats (0 when a size is refused or B == 0), 16-byte aligned.
+ * Limits: 0 <= B <= 4096 (B == 0 returns 0), 1 <= H <= 4096, W == 2H, 1 <= Ho <= 1024, 1 <= L <= 8, m <= 1e6 and not NaN.
+ * EML_EINVAL otherwise, and for a NULL pointer, with nothing enqueued. */
+size_t eml_env_prefilter_work_floats(int B, int H, int W, int Ho, int L);
+int eml_env_prefilter_f32(const float* pano, int B, int H, int W, int Ho, int L, const double* lobes, float* out, float* work,
+                          eml_stream_t stream);
+
+/* ---------------------------------------------------------------- object insertion: G-buffer shading and composite
+ * DESIGN.md section 22; the camera is RegressionNetwork/util.py:157-174 (`crop_panorama`'s ray of pixel (i, j), ratio = w / h)
+ * written in the panorama's frame of section 15.  One thread per pixel of a (B, ., h, w) G-buffer, all geometry in f64:
+ *   (c, s) = (cos, sin) of view_azimuth_deg;  f = (c, s, 0), r = (-s, c, 0), u = (0, 0, 1), v = -f
+ *   fov_deg > 0: scl = tan(fov / 2), sx = scl (2j / (w-1) - 1), sy = (scl h / w)(2i / (h-1) - 1),
+ *                v_p = -normalize(f + sx r - sy u);   fov_deg == 0 (orthographic): v_p = v
+ *   n = normalize(nx r + ny u + nz v) from normal (B,3,h,w),  R = 2 (n . v_p) n - v_p  (no special case for back faces)
+ *   shaded = kd * lookup(e_diffuse, n) + ks * lookup(e_phong, R) + km * lookup(pano, R)   products and sums in f32, in this order
+ * lookup(map of height G, dir): theta = atan2(sqrt(x^2 + y^2), z), phi = atan2(y, x) mod 2 pi (x, y = -0 count as +0: the
+ * poles themselves have phi = 0); continuous coordinates
+ * theta G / pi - 1/2 clamped to [0, G - 1] and phi 2G / 2 pi - 1/2 with wrapping columns, in f64; fractions rounded to f32;
+ * blend in f32, horizontal then vertical, a weight of 0 returns the tap (the mirror of eml_sphere_render_f32).
+ * kd, ks, km (B,3,h,w) or NULL: a term whose coefficient is NULL is not evaluated and its map is not read.  Where
+ * coverage (B,1,h,w) == 0 or the normal has length 0, shaded = 0 and neither the normal (at coverage 0) nor the coefficients
+ * are read.  Maps: pano (B,3,H,2H); e_diffuse (.,3,Hd,2Hd) and e_phong (.,3,Hg,2Hg) with d_stride / g_stride floats between
+ * the images' maps (a slice of eml_env_prefilter_f32's output: L 3 Hd 2Hd).
+ * Composite (epilogue, optional): background (B,3,h,w), exposure (B,) on the device, gamma > 0:
+ *   ldr = clamp(exposure[b] * shaded, 0, 1)^(1 / gamma)  (gamma == 1: no power),  composite = coverage ldr + (1 - coverage) background
+ * shaded and composite may each be NULL, not both.  kd, ks and km all NULL is the composite alone: shaded is then READ, not
+ * written, normal is not read (NULL is fine) and composite is required.
+ * Limits: 0 <= B <= 65535 (grid.y; B == 0 returns 0), 2 <= h, w and h w <= 2^29, 0 <= fov_deg < 180, map heights 1..4096.
+ * EML_EINVAL, with nothing enqueued: a NULL normal or coverage; kd, ks and km all NULL without shaded and composite; kd without e_diffuse, ks without
+ * e_phong, km without pano; a stride below 3 G 2G; composite without background or exposure, either of those without
+ * composite; gamma not > 0 with composite; non-finite angles; limits. */
+int eml_gbuffer_shade_f32(const float* pano, int H, const float* e_diffuse, int Hd, long d_stride, const float* e_phong, int Hg,
+                          long g_stride, const float* normal, const float* coverage, const float* kd, const float* ks,
+                          const float* km, int B, int h, int w, double fov_deg, double view_azimuth_deg, float* shaded,
+                          const float* background, const float* exposure, double gamma, float* composite,
+                          eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
