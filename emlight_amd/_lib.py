@@ -266,6 +266,14 @@ EXT_SIGNATURES = {
     "eml_gbuffer_shade_f32": (_int, [_f32p, _int, _f32p, _int, ctypes.c_long, _f32p, _int, ctypes.c_long, _f32p, _f32p, _f32p,
                                      _f32p, _f32p, _int, _int, _int, ctypes.c_double, ctypes.c_double, _f32p, _f32p, _f32p,
                                      ctypes.c_double, _f32p, _stream]),
+    # their adjoints: the exchanged implicit GEMM, and the 64-bit fixed-point scatter into the maps
+    "eml_env_prefilter_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int]),
+    "eml_env_prefilter_bwd_f32": (_int, [_f32p, _int, _int, _int, _int, _int, ctypes.c_void_p, _f32p, _f32p, _stream]),
+    "eml_gbuffer_shade_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int, _int, _int, _int, _int]),
+    "eml_gbuffer_shade_bwd_f32": (_int, [_f32p, _f32p, _int, _f32p, _int, ctypes.c_long, _f32p, _int, ctypes.c_long, _f32p,
+                                         _f32p, _f32p, _f32p, _f32p, _int, _int, _int, ctypes.c_double, ctypes.c_double,
+                                         _f32p, _f32p, ctypes.c_double, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                         _f32p, _stream]),
 }
 
 _lock = threading.Lock()

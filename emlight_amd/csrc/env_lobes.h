@@ -1,0 +1,48 @@
+// The lobe weights of the prefiltered environment maps, shared by the forward (env_prefilter.hip) and its adjoint
+// (env_prefilter_bwd.hip): both make k_l(omega_d . omega_t) from the SAME f32 grid tables, the same dot product and the same
+// lobe(), bit for bit (DESIGN.md sections 22 and 23).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace eml {
+namespace env {
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kThreads = 256;
+constexpr int kMaxHo = 1024, kMaxH = 4096, kMaxB = 4096, kMaxL = 8;
+constexpr int kNone = 0, kDiffuse = 1, kPhong = 2;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+inline bool size_ok(int B, int H, int W, int Ho, int L) {
+  return B >= 0 && B <= kMaxB && H >= 1 && H <= kMaxH && W == 2 * H && Ho >= 1 && Ho <= kMaxHo && L >= 1 && L <= kMaxL;
+}
+
+// texel (h, w) of a grid of height G: omega and dOmega in f64, rounded once
+static __global__ __launch_bounds__(kThreads) void grid_table_kernel(int G, float4* __restrict__ tab) {
+  const int t = blockIdx.x * kThreads + threadIdx.x, W = 2 * G;
+  if (t >= G * W) return;
+  const int h = t / W, w = t - h * W;
+  const double th = ((double)h + 0.5) * kPi / (double)G, ph = ((double)w + 0.5) * (2.0 * kPi) / (double)W;
+  const double st = sin(th);
+  tab[t] = make_float4((float)(st * cos(ph)), (float)(st * sin(ph)), (float)cos(th),
+                       (float)(st * (kPi / (double)G) * (2.0 * kPi / (double)W)));
+}
+
+// x^m for x >= 0 (x = 0: 1 when m == 0, as numpy's 0.0 ** 0)
+// Selects, not a branch: a divergent branch around the two transcendentals costs more than evaluating them on a safe argument
+__device__ __forceinline__ float lobe(float x, float m) {
+  const bool pos = x > 0.f;
+  const float p = exp2f(m * log2f(pos ? x : 1.f));
+  return pos ? p : (m == 0.f ? 1.f : 0.f);
+}
+template <int KIND>
+__device__ __forceinline__ float lobe_weight(float x, float m, float dom) {
+  return KIND == kDiffuse ? fmaxf(x, 0.f) * dom : lobe(x, m) * dom;
+}
+
+inline int kind_of(double v) { return v < 0.0 ? kDiffuse : kPhong; }
+inline double scale_of(double v) { return v < 0.0 ? 1.0 / kPi : (v + 1.0) / (2.0 * kPi); }
+
+}  // namespace env
+}  // namespace eml

@@ -15,20 +15,18 @@
 #include "eml_common.h"
 #include "../../include/emlight_hip_ext.h"
 
+#include "env_lobes.h"
+
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kThreads = 256;
+using namespace eml::env;                // the grid tables, lobe() and the limits: shared with env_prefilter_bwd.hip
+
 constexpr int kKC = 64;                 // texels per staged chunk
 constexpr int kColsWG = 96;             // image planes per workgroup: three 32-column MFMA tiles
 constexpr int kRowsWG = 128;            // directions per workgroup: one 32-row tile per wave
 constexpr int kStride = kKC + 1;        // LDS row of one plane's chunk, padded: the 32 lanes of a half hit 32 banks
 constexpr int kMaxSplit = 64;
 constexpr int kSlots = 512;             // 256 CUs x 2 resident workgroups
-constexpr int kMaxHo = 1024, kMaxH = 4096, kMaxB = 4096, kMaxL = 8;
-constexpr int kNone = 0, kDiffuse = 1, kPhong = 2;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Plan {
   long T, D;
@@ -49,33 +47,6 @@ inline Plan make_plan(int H, int Ho) {
   pl.splits = (pl.nchunks + pl.per - 1) / pl.per;
   return pl;
 }
-inline bool size_ok(int B, int H, int W, int Ho, int L) {
-  return B >= 0 && B <= kMaxB && H >= 1 && H <= kMaxH && W == 2 * H && Ho >= 1 && Ho <= kMaxHo && L >= 1 && L <= kMaxL;
-}
-
-// texel (h, w) of a grid of height G: omega and dOmega in f64, rounded once
-__global__ __launch_bounds__(kThreads) void grid_table_kernel(int G, float4* __restrict__ tab) {
-  const int t = blockIdx.x * kThreads + threadIdx.x, W = 2 * G;
-  if (t >= G * W) return;
-  const int h = t / W, w = t - h * W;
-  const double th = ((double)h + 0.5) * kPi / (double)G, ph = ((double)w + 0.5) * (2.0 * kPi) / (double)W;
-  const double st = sin(th);
-  tab[t] = make_float4((float)(st * cos(ph)), (float)(st * sin(ph)), (float)cos(th),
-                       (float)(st * (kPi / (double)G) * (2.0 * kPi / (double)W)));
-}
-
-// x^m for x >= 0 (x = 0: 1 when m == 0, as numpy's 0.0 ** 0)
-// Selects, not a branch: a divergent branch around the two transcendentals costs more than evaluating them on a safe argument
-__device__ __forceinline__ float lobe(float x, float m) {
-  const bool pos = x > 0.f;
-  const float p = exp2f(m * log2f(pos ? x : 1.f));
-  return pos ? p : (m == 0.f ? 1.f : 0.f);
-}
-template <int KIND>
-__device__ __forceinline__ float lobe_weight(float x, float m, float dom) {
-  return KIND == kDiffuse ? fmaxf(x, 0.f) * dom : lobe(x, m) * dom;
-}
-
 // grid (rowgroups, column groups of this launch, splits).  part[split][slot 0..1][direction][column].  NCT: the 32-column
 // tiles of a workgroup, a compile-time constant -- a guard around an MFMA inside the k loop makes the compiler carry that
 // accumulator through VGPRs (16 reads, 16 writes and a drain of the matrix pipe per iteration: measured 1.13 ms against
@@ -193,9 +164,6 @@ void launch_pass(const Plan& pl, hipStream_t s, const float* pano, const float4*
   else if (rest > 0) EML_TILES(1, 1, full * kColsWG);
 #undef EML_TILES
 }
-
-inline int kind_of(double v) { return v < 0.0 ? kDiffuse : kPhong; }
-inline double scale_of(double v) { return v < 0.0 ? 1.0 / kPi : (v + 1.0) / (2.0 * kPi); }
 
 }  // namespace
 

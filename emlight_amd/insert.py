@@ -9,7 +9,8 @@ estimation is for (the reference's README; its tree has no code for the step).  
   ``kd``, ``ks``, ``km``) lit by three lookups and composited over the photograph (``csrc/gbuffer_shade.hip``).
 * ``gbuffer_sphere``: the G-buffer of a sphere drawn as section 15 draws it, at a pixel position.
 
-Forward only: a tensor that requires grad is refused.  Everything only enqueues work.
+Forward only: a tensor that requires grad is refused (``emlight_amd.insert_grad`` is the differentiable interface).
+Everything only enqueues work.
 
     python -m emlight_amd.insert --pano pred.npy --image crop.npy --gbuffer DIR --fov 60 [--exposure A] [--out out.npy]
     python -m emlight_amd.insert --pano pred.npy --image crop.npy --sphere CX CY RADIUS [--kd 0.8 --ks 0.2 --km 0]
@@ -34,8 +35,8 @@ MAX_LOBES = 8
 
 def _forward_only(t, name):
     if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
-        raise ValueError("%s requires grad: object insertion is forward only (no gradient is defined); pass %s.detach()"
-                         % (name, name))
+        raise ValueError("%s requires grad: emlight_amd.insert is forward only (emlight_amd.insert_grad has the gradients of "
+                         "pano, maps, kd, ks, km and shaded); pass %s.detach()" % (name, name))
     return t
 
 

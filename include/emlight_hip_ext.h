@@ -213,6 +213,59 @@ int eml_gbuffer_shade_f32(const float* pano, int H, const float* e_diffuse, int 
                           const float* background, const float* exposure, double gamma, float* composite,
                           eml_stream_t stream);
 
+/* ---------------------------------------------------------------- object insertion: the adjoint of the prefilter
+ * DESIGN.md section 23 (the reference tree has no such code).  eml_env_prefilter_f32 is linear in the panorama; its gradient
+ * with respect to the panorama is the adjoint.  grad_out (B,L,3,Ho,2Ho) f32 -> dpano (B,3,H,W) f32, every element written:
+ *   dpano[b,ch,t] = dOmega_t sum_l c_l sum_d k_l(omega_d . omega_t) grad_out[b,l,ch,d]
+ * Grids, lobes (the same HOST array of L doubles, read before the call returns), c_l, 0^0 = 1 and the limits are those of
+ * eml_env_prefilter_f32, and so are the weights: the same f32 grid tables, the same dot product, the same x^m.  The same
+ * implicit GEMM on v_mfma_f32_32x32x2_f32, exchanged: rows are the 2 H^2 texels, k the (lobe, direction) pairs, columns the
+ * 3B planes.  All L lobes add into the same accumulators: one pass over grad_out serves any L.  c_l is applied to the staged
+ * grad_out, dOmega_t once per texel at the end.  No atomics: run-to-run exact.  The split over k is a function of (H, Ho)
+ * alone and is added in split order, so an image's gradient has the same bits in any batch.
+ * work: eml_env_prefilter_bwd_work_floats(B, H, W, Ho, L) floats (0 when a size is refused or B == 0), 16-byte aligned.
+ * EML_EINVAL on the conditions of eml_env_prefilter_f32 and for a NULL grad_out or dpano, with nothing enqueued; B == 0
+ * returns 0. */
+size_t eml_env_prefilter_bwd_work_floats(int B, int H, int W, int Ho, int L);
+int eml_env_prefilter_bwd_f32(const float* grad_out, int B, int H, int W, int Ho, int L, const double* lobes, float* dpano,
+                              float* work, eml_stream_t stream);
+
+/* ---------------------------------------------------------------- object insertion: the adjoint of shading and composite
+ * DESIGN.md section 23.  The inputs of eml_gbuffer_shade_f32 (maps with their strides, normal, coverage, kd / ks / km or
+ * NULL, the camera) and grad_out (B,3,h,w) f32.  Per pixel the frame, the taps, the fractions and the looked-up values are
+ * the forward's, bit for bit.  exposure == NULL: grad_out is the gradient of `shaded`, g_s = grad_out.  exposure (B,) given
+ * (with gamma): grad_out is the gradient of `composite`; the kernel recomputes s = shaded with the forward's f32 sequence,
+ * x = fl(exposure[b] s), and
+ *   g_s = grad_out coverage (1 / gamma) exposure[b] x^(1 / gamma - 1)   where 0 < x < 1,   g_s = 0 elsewhere
+ * (both clamps and the two boundaries give 0: the gradient is always finite; gamma == 1: grad_out coverage exposure[b]).
+ * The power is taken in f64 and g_s rounded to f32 once.  background takes no part.  Outputs, each may be NULL:
+ *   dkd, dks, dkm (B,3,h,w): g_s * lookup(e_diffuse, n), g_s * lookup(e_phong, R), g_s * lookup(pano, R), products in f32
+ *   d_e_diffuse (B,3,Hd,2Hd), d_e_phong (B,3,Hg,2Hg), dpano (B,3,H,2H; the mirror term only), contiguous, every element written:
+ *     dmap[b,ch,t] = sum over the taps (p, q) on texel t of w_q(p) k[b,ch,p] g_s[b,ch,p]
+ *     with (1-wx)(1-wy), wx (1-wy), (1-wx) wy, wx wy formed in f64 from the forward's f32 fractions
+ *   dshaded (B,3,h,w): g_s itself, in the composite-only mode (kd, ks, km all NULL), which READS shaded (B,3,h,w)
+ * A pixel with coverage 0 or a zero or non-finite normal gives exactly 0 everywhere and adds nothing; nothing of it but its
+ * coverage (and, at coverage != 0, its normal) is read.  Two taps of a pixel on one texel (a clamped row) both add; a texel
+ * nothing lands on is exactly 0.  The scatter is section 20's: per sample and map S = sum |k g_s| in f64 in a fixed order,
+ * the unit u = 2^(e - 61) with 2^e the power of two above S; each contribution is formed in f64, rounded once to a multiple
+ * of u and added with 64-bit integer atomics; one int64 -> f32 conversion.  |error before that rounding| <= n 2^-61 S for a
+ * texel n taps land on.  The bits do not depend on the arrival order, the batch, or the set of outputs asked for.
+ * Non-finite values in grad_out leave that sample's gradients unspecified; tap indices never depend on grad_out.  Only
+ * enqueues.  work: eml_gbuffer_shade_bwd_work_floats(...) floats (0 when a size is refused, B == 0 or no map gradient is
+ * wanted), 8-byte aligned; not read (NULL is fine) when no map gradient is wanted.  Limits as eml_gbuffer_shade_f32.
+ * EML_EINVAL, with nothing enqueued: a NULL grad_out, coverage or (with a coefficient) normal; no output; a gradient of a
+ * term whose coefficient is NULL; a coefficient without its map; shaded or dshaded with a coefficient, or the composite-only
+ * mode without shaded, exposure and dshaded; gamma not > 0 with exposure; non-finite angles; limits; a NULL or misaligned
+ * work when a map gradient is wanted and B > 0.  B == 0 returns 0. */
+size_t eml_gbuffer_shade_bwd_work_floats(int B, int H, int Hd, int Hg, int h, int w, int want_dpano, int want_d_e_diffuse,
+                                         int want_d_e_phong);
+int eml_gbuffer_shade_bwd_f32(const float* grad_out, const float* pano, int H, const float* e_diffuse, int Hd, long d_stride,
+                              const float* e_phong, int Hg, long g_stride, const float* normal, const float* coverage,
+                              const float* kd, const float* ks, const float* km, int B, int h, int w, double fov_deg,
+                              double view_azimuth_deg, const float* shaded, const float* exposure, double gamma, float* dkd,
+                              float* dks, float* dkm, float* d_e_diffuse, float* d_e_phong, float* dpano, float* dshaded,
+                              float* work, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
