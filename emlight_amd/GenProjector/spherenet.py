@@ -682,10 +682,14 @@ def sphere_max_pool(x, stride=1, return_indices=False):
 
 
 def _rows_view(t):
-    """(B,C,H,W) tensor in channels-last memory -> (its (B*H*W, C) row-major alias, row stride)."""
+    """(B,C,H,W) tensor in channels-last memory -> (its (B*H*W, C) row-major alias, row stride).  The kernels move 16 bytes per
+    lane: a view that starts off a 16-byte boundary (a channel slice from a channel that is no multiple of 4) is copied."""
     b, c, h, w = t.shape
-    if t.stride(1) != 1 or t.stride(3) % 4 or t.stride(2) != w * t.stride(3) or (b > 1 and t.stride(0) != h * t.stride(2)):
+    if (t.stride(1) != 1 or t.stride(3) % 4 or t.stride(2) != w * t.stride(3) or (b > 1 and t.stride(0) != h * t.stride(2))
+            or t.data_ptr() % 16):
         t = t.contiguous(memory_format=torch.channels_last)
+        if t.data_ptr() % 16:   # already dense, but inside a storage: a copy with a start of its own
+            t = t.clone(memory_format=torch.preserve_format)
     return t, t.stride(3)
 
 
