@@ -1,32 +1,18 @@
-// The lobe weights of the prefiltered environment maps, shared by the forward (env_prefilter.hip) and its adjoint
-// (env_prefilter_bwd.hip): both make k_l(omega_d . omega_t) from the SAME f32 grid tables, the same dot product and the same
-// lobe(), bit for bit (DESIGN.md sections 22 and 23).
+// The lobe weights of the sphere renders (sphere_render.hip) and of the prefiltered environment maps, forward
+// (env_prefilter.hip) and adjoint (env_prefilter_bwd.hip): all make k_l(omega_d . omega_t) from the SAME f32 grid tables
+// (sphere_gemm.h), the same dot product and the same lobe(), bit for bit (DESIGN.md sections 15, 22 and 23).
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sphere_gemm.h"
 
 namespace eml {
 namespace env {
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kThreads = 256;
+using sgemm::kPi;
 constexpr int kMaxHo = 1024, kMaxH = 4096, kMaxB = 4096, kMaxL = 8;
 constexpr int kNone = 0, kDiffuse = 1, kPhong = 2;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 inline bool size_ok(int B, int H, int W, int Ho, int L) {
   return B >= 0 && B <= kMaxB && H >= 1 && H <= kMaxH && W == 2 * H && Ho >= 1 && Ho <= kMaxHo && L >= 1 && L <= kMaxL;
-}
-
-// texel (h, w) of a grid of height G: omega and dOmega in f64, rounded once
-static __global__ __launch_bounds__(kThreads) void grid_table_kernel(int G, float4* __restrict__ tab) {
-  const int t = blockIdx.x * kThreads + threadIdx.x, W = 2 * G;
-  if (t >= G * W) return;
-  const int h = t / W, w = t - h * W;
-  const double th = ((double)h + 0.5) * kPi / (double)G, ph = ((double)w + 0.5) * (2.0 * kPi) / (double)W;
-  const double st = sin(th);
-  tab[t] = make_float4((float)(st * cos(ph)), (float)(st * sin(ph)), (float)cos(th),
-                       (float)(st * (kPi / (double)G) * (2.0 * kPi / (double)W)));
 }
 
 // x^m for x >= 0 (x = 0: 1 when m == 0, as numpy's 0.0 ** 0)

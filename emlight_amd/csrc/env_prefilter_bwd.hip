@@ -1,50 +1,23 @@
 // Object insertion: the adjoint of the prefiltered environment maps (env_prefilter.hip; DESIGN.md section 23;
 // tests/insert_grad_oracle.py restates the definition in float64).
 //
-// dpano = dOmega . K^T . grad_out: the forward's implicit GEMM, exchanged.  Rows: the 2 H^2 texels -- a wave owns 32 of
-// them and keeps their omega in registers; k: the (lobe, direction) pairs; columns: the 3B planes.  The A fragment of
-// v_mfma_f32_32x32x2_f32 (lane l: texel l & 31, direction k + (l >> 5)) is built from the direction table in LDS beside the
-// staged chunk of grad_out, with the forward's dot product (direction first) and the forward's lobe().  Unlike the forward,
-// every lobe adds into the SAME accumulators (3 column tiles x 16 registers): one pass serves any L.  The lobe loop is
-// outside the chunk loop; the diffuse lobes come first and the Phong lobes second, each kind with its own instantiated
-// inner loop, so the kind is a wave-uniform choice made once, not per element.  c_l is applied when a chunk is staged to
-// LDS, dOmega_t once per row by the reduction.  The directions are split over grid.z; the partial tiles go to scratch and a
-// second launch adds them in split order (no atomics: run-to-run exact).  The split depends on (H, Ho) only and an MFMA
-// adds its k terms in order per output element: an image's gradient does not depend on the batch.
+// dpano = dOmega . K^T . grad_out: the forward's implicit GEMM (sphere_gemm.h), exchanged.  Rows: the 2 H^2 texels -- a wave
+// keeps its 32 omega in registers; reduction: the (lobe, direction) pairs, the directions split; columns: the 3B planes.
+// The weight is made with the forward's dot product (direction first) and the forward's lobe().  Unlike the forward, every
+// lobe adds into the SAME accumulators (3 column tiles x 16 registers): one pass serves any L.  The lobe loop is outside
+// the chunk loop; the diffuse lobes come first and the Phong lobes second, each kind with its own instantiated inner loop,
+// so the kind is a wave-uniform choice made once, not per element.  c_l is applied when a chunk is staged to LDS, dOmega_t
+// once per row by the reduction.
 #include "eml_common.h"
 #include "../../include/emlight_hip_ext.h"
+#include <type_traits>
+
 #include "env_lobes.h"
 
 namespace {
 
 using namespace eml::env;
-
-constexpr int kKC = 64;                 // directions per staged chunk
-constexpr int kColsWG = 96;             // image planes per workgroup: three 32-column MFMA tiles
-constexpr int kRowsWG = 128;            // texels per workgroup: one 32-row tile per wave
-constexpr int kStride = kKC + 1;        // LDS row of one plane's chunk, padded: the 32 lanes of a half hit 32 banks
-constexpr int kMaxSplit = 64;
-constexpr int kSlots = 512;             // 256 CUs x 2 resident workgroups
-
-struct Plan {
-  long T, D;
-  int nchunks, per, splits, rowgroups;
-};
-// the k split is a function of (H, Ho) alone: an image's summation order must not depend on the batch
-inline Plan make_plan(int H, int Ho) {
-  Plan pl;
-  pl.T = 2l * H * H;
-  pl.D = 2l * Ho * Ho;
-  pl.nchunks = (int)((pl.D + kKC - 1) / kKC);
-  pl.rowgroups = (int)((pl.T + kRowsWG - 1) / kRowsWG);
-  int want = kSlots / pl.rowgroups;                  // one column group's workgroups fit the part at once
-  if (want > kMaxSplit) want = kMaxSplit;
-  if (want > pl.nchunks) want = pl.nchunks;
-  if (want < 1) want = 1;
-  pl.per = (pl.nchunks + want - 1) / want;
-  pl.splits = (pl.nchunks + pl.per - 1) / pl.per;
-  return pl;
-}
+using namespace eml::sgemm;
 
 // the lobes in the order they are added: the diffuse ones first, then the Phong ones, each group in the caller's order
 struct Lobes {
@@ -53,135 +26,95 @@ struct Lobes {
   float m[kMaxL], c[kMaxL];
 };
 
-// one staged chunk: 64 directions against the wave's 32 texels.  No guard around an MFMA: columns beyond the batch hold zeros
-template <int KIND, int NCT>
-__device__ __forceinline__ void chunk_mac(const float* __restrict__ sp, const float4* __restrict__ st, float tx, float ty,
-                                          float tz, float m, int half, int r, f32x16 (&acc)[NCT]) {
-#pragma unroll 2
-  for (int kk = 0; kk < kKC; kk += 2) {
-    const float4 o = st[kk + half];
-    const float x = fmaf(o.x, tx, fmaf(o.y, ty, o.z * tz));              // the forward's dot product: direction first
-    const float wa = KIND == kDiffuse ? fmaxf(x, 0.f) : lobe(x, m);
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      const float b = sp[(ct * 32 + r) * kStride + kk + half];
-      acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, b, acc[ct], 0, 0, 0);
-    }
-  }
-}
-
 // grid (rowgroups, column groups of this launch, splits).  part[split][texel][column].  g (B, L, 3, D).  NCT: the 32-column
-// tiles of a workgroup, a compile-time constant (env_prefilter.hip has the measurement behind that).
+// tiles of a workgroup, a compile-time constant and no guard in the k loop (env_prefilter.hip has the measurement behind
+// that): columns beyond the batch hold zeros.
 template <int NCT>
 __global__ __launch_bounds__(kThreads) void prefilter_bwd_kernel(const float* __restrict__ g, const float4* __restrict__ tab,
                                                                  const float4* __restrict__ dtab, int D, int T, int N,
                                                                  int col_base, int per, int nchunks, Lobes lb,
                                                                  float* __restrict__ part) {
-  constexpr int kCols = NCT * 32;
+  constexpr int kCols = NCT * 32, kLoads = kCols * kKC / kThreads;
   __shared__ float sp[kCols * kStride];
   __shared__ float4 st[kKC];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
-  const int t = blockIdx.x * kRowsWG + wave * 32 + r;
+  const Lanes ln = lanes();
+  const int tid = ln.tid;
   float tx = 0.f, ty = 0.f, tz = 0.f;                                    // a row beyond T is never stored
-  if (t < T) {
-    const float4 q = tab[t];
+  if (ln.row < T) {
+    const float4 q = tab[ln.row];
     tx = q.x, ty = q.y, tz = q.z;
   }
   const int col0 = col_base + blockIdx.y * kCols;
   const int ncols = N - col0 < kCols ? N - col0 : kCols;                 // > 0 by the grid
-  f32x16 acc[NCT];
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[ct][e] = 0.f;
+  f32x16 acc[1][NCT];
+  zero(acc[0]);
 
-  const int c_begin = blockIdx.z * per;
-  const int c_end = c_begin + per < nchunks ? c_begin + per : nchunks;   // > c_begin by the plan
-  constexpr int kLoads = kCols * kKC / kThreads;                         // 8 values per thread, tile and chunk
+  const ChunkRange cr = split_chunks(per, nchunks);                      // end > begin by the plan
   // this thread's columns: plane col = 3 b + ch of lobe l starts at ((b L + l) 3 + ch) D = (col + 3 b (L - 1) + 3 l) D
   size_t src[kLoads];
-#pragma unroll
-  for (int e = 0; e < kLoads; ++e) {
-    const int cl = (e * kThreads + tid) >> 6, col = col0 + (cl < ncols ? cl : 0);
+  for_each_load<NCT>(tid, [&](int e, int cl, int) {
+    const int col = col0 + (cl < ncols ? cl : 0);
     src[e] = (size_t)(col + 3 * (col / 3) * (lb.n - 1)) * (size_t)D;
-  }
+  });
   float pre[kLoads];
   float4 pre_t;
-  // chunk c of lobe l -> registers; a wave reads 64 consecutive directions of one plane.  A direction beyond D: zero operand
-  auto fetch = [&](int l, int c) {
+  // The steps of this workgroup: lobe slot li (diffuse lobes first), chunk c.  (li, c) is a running cursor, not a function of
+  // the step number (no division per chunk): stage() reads c_l and m of the step it stages and THEN moves the cursor to the
+  // step that pipeline() fetches next, so fetch() takes the cursor as it finds it -- the call order is pipeline()'s contract.
+  // A wave reads 64 consecutive directions of one plane; a direction beyond D: zero operand
+  const int nc = cr.end - cr.begin, total = lb.n * nc, diffuse_steps = lb.n_diffuse * nc;
+  int li = 0, c = cr.begin;
+  float m_staged = 0.f;                                                  // the exponent of the step in LDS
+  auto fetch = [&](int) {
     const int k0 = c * kKC;
-    const size_t lobe_off = (size_t)(3 * l) * (size_t)D;
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid, cl = idx >> 6, k = k0 + (idx & (kKC - 1));
-      pre[e] = (cl < ncols && k < D) ? g[src[e] + lobe_off + k] : 0.f;
-    }
+    const size_t lobe_off = (size_t)(3 * lb.index[li]) * (size_t)D;
+    for_each_load<NCT>(tid, [&](int e, int cl, int k) {
+      pre[e] = (cl < ncols && k0 + k < D) ? g[src[e] + lobe_off + k0 + k] : 0.f;
+    });
     pre_t = (tid < kKC && k0 + tid < D) ? dtab[k0 + tid] : make_float4(0.f, 0.f, 0.f, 0.f);
   };
-  // the steps of this workgroup: lobe slot li (diffuse lobes first), chunk c; step + 1 is fetched while step is computed
-  const int nc = c_end - c_begin, total = lb.n * nc;
-  int li = 0, c = c_begin, step = 0;
-  fetch(lb.index[0], c_begin);
   auto stage = [&]() {
     const float cl = lb.c[li];
-    __syncthreads();                                                     // the previous chunk has been read
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid;
-      sp[(idx >> 6) * kStride + (idx & (kKC - 1))] = pre[e] * cl;        // c_l here: once per value, not per MFMA operand
-    }
+    m_staged = lb.m[li];
+    stage_plane<NCT>(sp, pre, tid, cl);                                  // c_l here: once per value, not per MFMA operand
     if (tid < kKC) st[tid] = pre_t;
-    __syncthreads();
-    ++step, ++c;
-    if (c == c_end) c = c_begin, ++li;
-    if (step < total) fetch(lb.index[li], c);                            // in flight while this chunk is computed
+    if (++c == cr.end) c = cr.begin, ++li;                               // now the step that is fetched next
+  };
+  auto mac = [&](auto kind) {
+    const float m = m_staged;                                            // by value: loop-invariant for the k loop
+    chunk_mac<NCT, 1, true, false, true>(sp, ncols, ln, [&](int k, float (&w)[1]) {
+      const float4 o = st[k];
+      const float x = fmaf(o.x, tx, fmaf(o.y, ty, o.z * tz));            // the forward's dot product: direction first
+      w[0] = decltype(kind)::value == kDiffuse ? fmaxf(x, 0.f) : lobe(x, m);
+    }, acc);
   };
   // two loops, not a choice inside one: the accumulators stay where they are (a branch between two instantiated inner
   // loops per chunk made the compiler move all 48 registers in and out around it)
-  const int diffuse_steps = lb.n_diffuse * nc;
-  while (step < diffuse_steps) {
-    stage();
-    chunk_mac<kDiffuse, NCT>(sp, st, tx, ty, tz, 1.f, half, r, acc);
-  }
-  while (step < total) {
-    const float m = lb.m[li];
-    stage();
-    chunk_mac<kPhong, NCT>(sp, st, tx, ty, tz, m, half, r, acc);
-  }
-  // C/D of the 32x32 tile: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+  fetch(0);
+  pipeline(0, diffuse_steps, total, fetch, stage, [&]() { mac(std::integral_constant<int, kDiffuse>()); });
+  pipeline(diffuse_steps, total, total, fetch, stage, [&]() { mac(std::integral_constant<int, kPhong>()); });
+
   float* pd = part + (size_t)blockIdx.z * (size_t)T * (size_t)N;
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    const int cl = ct * 32 + r;
-    if (cl >= ncols) continue;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = blockIdx.x * kRowsWG + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-      if (row >= T) continue;
-      pd[(size_t)row * N + col0 + cl] = acc[ct][e];
-    }
-  }
+  for_each_c<NCT>(ln, [&](int ct, int e, int i, int j) {
+    const int row = ln.row0 + i, cl = ct * 32 + j;
+    if (cl < ncols && row < T) pd[(size_t)row * N + col0 + cl] = acc[0][ct][e];
+  });
 }
 
-// dpano[col][texel] = dOmega_t * sum over the splits, in split order
-__global__ __launch_bounds__(kThreads) void prefilter_bwd_reduce_kernel(const float* __restrict__ part,
-                                                                        const float4* __restrict__ tab, int T, int N,
-                                                                        int splits, float* __restrict__ dpano) {
-  const size_t plane = (size_t)T * (size_t)N;
-  const size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (e >= plane) return;
-  const int t = (int)(e / N), col = (int)(e - (size_t)t * N);
-  float s = 0.f;
-  for (int k = 0; k < splits; ++k) s += part[(size_t)k * plane + e];
-  dpano[(size_t)col * (size_t)T + t] = s * tab[t].w;
-}
+// dpano[col][texel] = dOmega_t * the sum over the splits
+struct StoreGradient {
+  const float4* tab;
+  int T;
+  float* dpano;
+  __device__ void operator()(int t, int col, int, float s) const { dpano[(size_t)col * (size_t)T + t] = s * tab[t].w; }
+};
 
 }  // namespace
 
 extern "C" size_t eml_env_prefilter_bwd_work_floats(int B, int H, int W, int Ho, int L) {
   if (!size_ok(B, H, W, Ho, L) || B == 0) return 0;
-  const Plan pl = make_plan(H, Ho);
-  return 4 * (size_t)pl.T + 4 * (size_t)pl.D + (size_t)pl.splits * pl.T * 3 * (size_t)B;
+  const size_t T = 2 * (size_t)H * H, D = 2 * (size_t)Ho * Ho;
+  return 4 * T + 4 * D + (size_t)make_split_plan(T, D).splits * T * 3 * (size_t)B;
 }
 
 extern "C" int eml_env_prefilter_bwd_f32(const float* grad_out, int B, int H, int W, int Ho, int L, const double* lobes,
@@ -211,13 +144,13 @@ extern "C" int eml_env_prefilter_bwd_f32(const float* grad_out, int B, int H, in
   if (((size_t)work) & 15) return eml::fail(EML_EINVAL, "eml_env_prefilter_bwd_f32: work must be 16-byte aligned");
   if (B == 0) return EML_OK;
   hipStream_t s = (hipStream_t)stream;
-  const Plan pl = make_plan(H, Ho);
-  const int D = (int)pl.D, T = (int)pl.T, N = 3 * B;
+  const int D = 2 * Ho * Ho, T = 2 * H * H, N = 3 * B;
+  const SplitPlan pl = make_split_plan(T, D);               // of (H, Ho) alone: not of the batch
   float4* tab = reinterpret_cast<float4*>(work);
   float4* dtab = tab + T;
   float* part = work + 4 * (size_t)T + 4 * (size_t)D;
-  hipLaunchKernelGGL(grid_table_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, tab);
-  hipLaunchKernelGGL(grid_table_kernel, dim3((D + kThreads - 1) / kThreads), dim3(kThreads), 0, s, Ho, dtab);
+  hipLaunchKernelGGL(grid_table_kernel<>, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, tab);
+  hipLaunchKernelGGL(grid_table_kernel<>, dim3((D + kThreads - 1) / kThreads), dim3(kThreads), 0, s, Ho, dtab);
   int rc = eml::check_launch("eml_env_prefilter_bwd_f32(tables)");
   if (rc) return rc;
   // the full groups of 96 columns in one launch, the remaining 1..95 columns in a second with as many tiles as they need
@@ -232,8 +165,6 @@ extern "C" int eml_env_prefilter_bwd_f32(const float* grad_out, int B, int H, in
 #undef EML_TILES
   rc = eml::check_launch("eml_env_prefilter_bwd_f32(integral)");
   if (rc) return rc;
-  const size_t plane = (size_t)T * N;
-  hipLaunchKernelGGL(prefilter_bwd_reduce_kernel, dim3((unsigned)((plane + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                     (const float*)part, (const float4*)tab, T, N, pl.splits, dpano);
+  launch_split_reduce(s, part, T, N, pl.splits, 1, 0, 1, StoreGradient{tab, T, dpano});
   return eml::check_launch("eml_env_prefilter_bwd_f32");
 }

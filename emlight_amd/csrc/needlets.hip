@@ -7,48 +7,22 @@
 // sum through the spherical harmonics of x).  A level's coefficients beyond its own 2^(j+1) are zero, so every row runs the
 // same Legendre recurrence and the rows of one tile may span levels without a branch.
 //
-// Analysis (coeffs = Psi^T . (w * pano), gt_gen_j3.py:39-43) and synthesis (rec = w * Psi . coeffs, mat_gen2.py:55) are one
-// implicit GEMM on v_mfma_f32_32x32x2_f32 whose Psi operand is built in registers, as sphere_render.hip builds its weights:
-// a lane keeps its row's vector (a centre / a pixel direction), the reduction chunk (pixels / basis rows: vector, weight or
-// level, and the 3B image planes) is staged in LDS.  Analysis splits the pixels over grid.z, writes partial tiles to scratch
-// and a second launch adds them in split order (no atomics: run-to-run exact); the split depends on (P, jmax) only and an MFMA
-// adds its k terms in order per output element, so an image's coefficients do not depend on the batch it came in.
+// Analysis (coeffs = Psi^T . (w * pano), gt_gen_j3.py:39-43) and synthesis (rec = w * Psi . coeffs, mat_gen2.py:55) are the
+// implicit GEMM of sphere_gemm.h with Psi as the weight: a lane keeps its row's vector (a centre / a pixel direction), the
+// reduction chunk (pixels / basis rows: vector, weight or level, and the 3B image planes) is staged in LDS.  Analysis
+// splits the pixels; synthesis is not split.
 #include "eml_common.h"
+#include "sphere_gemm.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kKC = 64;                 // reduction entries per staged chunk
-constexpr int kColsWG = 96;             // image planes per workgroup: three 32-wide MFMA tiles
-constexpr int kRowsWG = 128;            // rows per workgroup: one 32-row tile per wave
-constexpr int kStride = kKC + 1;        // LDS row of one plane's chunk, padded: the 32 lanes of a half hit 32 banks
-constexpr int kMaxSplit = 64;
-constexpr int kSlots = 512;
+using namespace eml::sgemm;
+
 constexpr int kLmax = 32, kTabRow = kLmax + 1, kMaxLevels = 6;     // table rows: Y_00, levels 0..4
 constexpr int kMaxB = 65535, kMaxP = 1 << 24;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 inline int rows_of(int jmax) { return (1 << (2 * (jmax + 2))) - 3; }             // 1 + 12 (1 + 4 + ... + 4^jmax)
 __host__ __device__ inline int level_start(int j) { return (1 << (2 * (j + 1))) - 3; }   // first row of level j
-
-struct Plan {
-  int K, nchunks, per, splits, rowgroups;
-};
-// the pixel split is a function of (P, jmax) alone: an image's summation order must not depend on the batch
-inline Plan make_plan(int P, int jmax) {
-  Plan pl;
-  pl.K = rows_of(jmax);
-  pl.nchunks = (P + kKC - 1) / kKC;
-  pl.rowgroups = (pl.K + kRowsWG - 1) / kRowsWG;
-  int want = kSlots / pl.rowgroups;
-  if (want > kMaxSplit) want = kMaxSplit;
-  if (want > pl.nchunks) want = pl.nchunks;
-  if (want < 1) want = 1;
-  pl.per = (pl.nchunks + want - 1) / want;
-  pl.splits = (pl.nchunks + pl.per - 1) / pl.per;
-  return pl;
-}
 
 // sum_{l <= L} c[l] P_l(t): three-term recurrence l P_l = (2l-1) t P_{l-1} - (l-1) P_{l-2}
 template <int L>
@@ -92,7 +66,9 @@ __global__ __launch_bounds__(kThreads) void basis_kernel(const float* __restrict
 // SYNTH == false (analysis): rows = basis functions (R = K), reduction = pixels (T = P), src = pano (N, P);
 //   grid (rowgroups, colgroups, splits), dst = part[split][k][column].
 // SYNTH == true: rows = pixels (R = P), reduction = basis functions (T = K), src = coeffs (B, K, 3);
-//   grid (rowgroups, colgroups, 1), dst = rec (N, P), written directly.
+//   grid (rowgroups, colgroups, 1), dst = rec (N, P), written directly: the weight is the MFMA's B operand, C[plane][pixel],
+//   so that a store runs along the pixels.
+// Three column tiles under the guard; the entry loop is left to the compiler (psi<L> is long).
 template <int L, bool SYNTH>
 __global__ __launch_bounds__(kThreads) void gemm_kernel(const float* __restrict__ src, const float4* __restrict__ cen,
                                                         const float* __restrict__ dirs, const float* __restrict__ wts,
@@ -101,9 +77,9 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const float* __restrict_
   __shared__ float sp[kColsWG * kStride];
   __shared__ float4 st[kKC];
   __shared__ float sc[(kMaxLevels + 1) * kTabRow];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+  const Lanes ln = lanes();
+  const int tid = ln.tid, row = ln.row;
   const int R = SYNTH ? P : K, T = SYNTH ? K : P;
-  const int row = blockIdx.x * kRowsWG + wave * 32 + r;
   load_table(ctab, nlev, sc);
   __syncthreads();
   float vx = 0.f, vy = 0.f, vz = 0.f, wrow = 1.f;
@@ -124,29 +100,23 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const float* __restrict_
   }
   const int col0 = blockIdx.y * kColsWG;
   const int ncols = N - col0 < kColsWG ? N - col0 : kColsWG;             // > 0 by the grid
-  f32x16 acc[3];
-#pragma unroll
-  for (int ct = 0; ct < 3; ++ct)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[ct][e] = 0.f;
+  f32x16 acc[1][3];
+  zero(acc[0]);
 
-  const int c_begin = blockIdx.z * per;
-  const int c_end = c_begin + per < nchunks ? c_begin + per : nchunks;
-  constexpr int kLoads = kColsWG * kKC / kThreads;                       // 24 values per thread and chunk
-  float pre[kLoads];
+  const ChunkRange chunks = split_chunks(per, nchunks);
+  float pre[kColsWG * kKC / kThreads];
   float4 pre_t;
-  auto fetch = [&](int c) {
-    const int k0 = c * kKC;
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid, cl = idx >> 6, k = k0 + (idx & (kKC - 1));
+  auto fetch = [&](int step) {
+    const int k0 = (chunks.begin + step) * kKC;
+    for_each_load<3>(tid, [&](int e, int cl, int ko) {
+      const int k = k0 + ko;
       float v = 0.f;
       if (cl < ncols && k < T) {
         const int col = col0 + cl;
         v = SYNTH ? src[((size_t)(col / 3) * K + k) * 3 + col % 3] : src[(size_t)col * (size_t)P + k];
       }
       pre[e] = v;
-    }
+    });
     pre_t = make_float4(0.f, 0.f, 0.f, SYNTH ? (float)nlev : 0.f);        // beyond T: the zero row / weight 0
     if (tid < kKC && k0 + tid < T) {
       if (SYNTH) pre_t = cen[k0 + tid];
@@ -156,60 +126,35 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const float* __restrict_
       }
     }
   };
-  if (c_begin < c_end) fetch(c_begin);
-  for (int c = c_begin; c < c_end; ++c) {
-    __syncthreads();                                                     // the previous chunk has been read
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid;
-      sp[(idx >> 6) * kStride + (idx & (kKC - 1))] = pre[e];
-    }
+  auto stage = [&]() {
+    stage_plane<3>(sp, pre, tid);
     if (tid < kKC) st[tid] = pre_t;
-    __syncthreads();
-    if (c + 1 < c_end) fetch(c + 1);                                     // in flight while this chunk is computed
-    for (int kk = 0; kk < kKC; kk += 2) {
-      const float4 t = st[kk + half];
-      const float d = fmaf(vx, t.x, fmaf(vy, t.y, vz * t.z));
-      const float a = SYNTH ? psi<L>(sc + (int)t.w * kTabRow, d) : psi<L>(cr, d) * t.w;
-#pragma unroll
-      for (int ct = 0; ct < 3; ++ct) {
-        if (ct * 32 < ncols) {                                           // wave-uniform
-          const float b = sp[(ct * 32 + r) * kStride + kk + half];
-          // analysis: C[basis row][plane];  synthesis: C[plane][pixel], so that a store runs along the pixels
-          acc[ct] = SYNTH ? __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc[ct], 0, 0, 0)
-                          : __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[ct], 0, 0, 0);
-        }
-      }
+  };
+  auto weight = [&](int k, float (&w)[1]) {
+    const float4 t = st[k];
+    const float d = fmaf(vx, t.x, fmaf(vy, t.y, vz * t.z));
+    w[0] = SYNTH ? psi<L>(sc + (int)t.w * kTabRow, d) : psi<L>(cr, d) * t.w;
+  };
+  pipeline(chunks.end - chunks.begin, fetch, stage,
+           [&]() { chunk_mac<3, 1, !SYNTH, true, false>(sp, ncols, ln, weight, acc); });
+
+  for_each_c<3>(ln, [&](int ct, int e, int i, int j) {
+    if (SYNTH) {
+      const int cl = ct * 32 + i;
+      if (cl < ncols && row < P) dst[(size_t)(col0 + cl) * (size_t)P + row] = acc[0][ct][e] * wrow;
+    } else {
+      const int cl = ct * 32 + j, k = ln.row0 + i;
+      if (cl < ncols && k < K) dst[((size_t)blockIdx.z * K + k) * (size_t)N + col0 + cl] = acc[0][ct][e];
     }
-  }
-  // C/D of the 32x32 tile: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
-#pragma unroll
-  for (int ct = 0; ct < 3; ++ct) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int i = (e & 3) + 8 * (e >> 2) + 4 * half;
-      if (SYNTH) {
-        const int cl = ct * 32 + i;
-        if (cl < ncols && row < P) dst[(size_t)(col0 + cl) * (size_t)P + row] = acc[ct][e] * wrow;
-      } else {
-        const int cl = ct * 32 + r, k = blockIdx.x * kRowsWG + wave * 32 + i;
-        if (cl < ncols && k < K) dst[((size_t)blockIdx.z * K + k) * (size_t)N + col0 + cl] = acc[ct][e];
-      }
-    }
-  }
+  });
 }
 
-// coeffs[b][k][ch] = sum over the splits, in split order
-__global__ __launch_bounds__(kThreads) void analysis_reduce_kernel(const float* __restrict__ part, int K, int N, int splits,
-                                                                   float* __restrict__ out) {
-  const size_t plane = (size_t)K * (size_t)N;
-  const size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (e >= plane) return;
-  const int k = (int)(e / N), col = (int)(e - (size_t)k * N);
-  float s = 0.f;
-  for (int z = 0; z < splits; ++z) s += part[(size_t)z * plane + e];
-  out[((size_t)(col / 3) * K + k) * 3 + col % 3] = s;
-}
+// coeffs[b][k][ch] = the sum over the splits
+struct StoreCoeffs {
+  int K;
+  float* out;
+  __device__ void operator()(int k, int col, int, float s) const { out[((size_t)(col / 3) * K + k) * 3 + col % 3] = s; }
+};
 
 // ------------------------------------------------------------------------------------------------ sparsify
 // grid (jmax + 2, B): block x = 0 copies row 0 (Y_00), block x = j + 1 owns level j of image y
@@ -285,8 +230,7 @@ inline bool jmax_ok(int jmax) { return jmax >= 0 && jmax <= 4; }
 
 extern "C" size_t eml_needlet_work_floats(int P, int jmax, int B) {
   if (!jmax_ok(jmax) || P < 1 || P > kMaxP || B < 1 || B > kMaxB) return 0;
-  const Plan pl = make_plan(P, jmax);
-  return (size_t)pl.splits * pl.K * 3 * (size_t)B;
+  return (size_t)make_split_plan(rows_of(jmax), P).splits * rows_of(jmax) * 3 * (size_t)B;
 }
 
 extern "C" int eml_needlet_basis_f32(const float* dirs, int P, const float* centres, const float* ctab, int jmax, float* out,
@@ -315,8 +259,8 @@ extern "C" int eml_needlet_analysis_f32(const float* pano, const float* dirs, co
     return eml::fail(EML_EINVAL, "eml_needlet_analysis_f32: work and centres must be 16-byte aligned");
   if (B == 0) return EML_OK;
   hipStream_t s = (hipStream_t)stream;
-  const Plan pl = make_plan(P, jmax);
-  const int K = pl.K, N = 3 * B, nlev = jmax + 2;
+  const int K = rows_of(jmax), N = 3 * B, nlev = jmax + 2;
+  const SplitPlan pl = make_split_plan(K, P);               // of (P, jmax) alone: not of the batch
   const float4* cen = reinterpret_cast<const float4*>(centres);
   const dim3 grid(pl.rowgroups, (N + kColsWG - 1) / kColsWG, pl.splits);
 #define CALL(L) launch_gemm<L, false>(grid, s, pano, cen, dirs, weights, ctab, nlev, K, P, N, pl.per, pl.nchunks, work)
@@ -324,9 +268,7 @@ extern "C" int eml_needlet_analysis_f32(const float* pano, const float* dirs, co
 #undef CALL
   int rc = eml::check_launch("eml_needlet_analysis_f32(partial)");
   if (rc) return rc;
-  const size_t plane = (size_t)K * N;
-  hipLaunchKernelGGL(analysis_reduce_kernel, dim3((unsigned)((plane + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                     (const float*)work, K, N, pl.splits, coeffs);
+  launch_split_reduce(s, work, K, N, pl.splits, 1, 0, 1, StoreCoeffs{K, coeffs});
   return eml::check_launch("eml_needlet_analysis_f32");
 }
 

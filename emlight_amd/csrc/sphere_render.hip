@@ -4,35 +4,26 @@
 // section 15 is the definition, tests/sphere_render_oracle.py restates it in float64.
 //
 // Diffuse and glossy are integrals over the panorama: render = K . pano with K (inside pixels x texels) the cosine /
-// Phong-lobe weights times the texel's solid angle, pano (texels x 3B image planes).  K is never stored: a wave owns 32
-// pixels, keeps their n and R in registers, and builds its A fragment of v_mfma_f32_32x32x2_f32 (lane l: pixel l & 31,
-// texel k + (l >> 5)) from a per-texel table (omega, dOmega) that sits in LDS beside the staged panorama chunk; the same
-// chunk feeds both materials' accumulators.  The texels are split over grid.z; the partial tiles go to scratch and a
-// second launch adds them in split order (no atomics: run-to-run exact).  The split depends on (H, W, S) only and an
-// MFMA adds its k terms in order per output element, so an image's render does not depend on the batch it came in.
-// Mirror is a bilinear gather at the reflection direction, coordinates in f64.  Metrics: one workgroup per (image,
-// material), f64 tree reductions in a fixed order (as gt_param.hip), two passes so that si-RMSE is a sum of squares of
-// residuals and not a difference of large sums.
+// Phong-lobe weights times the texel's solid angle, pano (texels x 3B image planes), on the implicit GEMM of sphere_gemm.h:
+// rows = inside pixels (a wave keeps its 32 n and R in registers), reduction = texels (table entry: omega, dOmega), split;
+// the same chunk feeds both materials' accumulators.  Mirror is a bilinear gather at the reflection direction, coordinates
+// in f64.  Metrics: one workgroup per (image, material), f64 tree reductions in a fixed order (as gt_param.hip), two passes
+// so that si-RMSE is a sum of squares of residuals and not a difference of large sums.
 //
 // The renders are linear in the panorama; their gradient with respect to it (the render loss) is the adjoint: the same
 // implicit GEMM with pixels and texels exchanged, plus the mirror's taps sorted by texel (see adjoint_kernel below).
 #include "eml_common.h"
 #include "../../include/emlight_hip_ext.h"
 
+#include "env_lobes.h"
+
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kThreads = 256;
-constexpr int kKC = 64;                 // texels per staged chunk
-constexpr int kColsWG = 96;             // image planes per workgroup: three 32-column MFMA tiles
-constexpr int kRowsWG = 128;            // pixels per workgroup: one 32-row tile per wave
-constexpr int kStride = kKC + 1;        // LDS row of one plane's chunk, padded: the 32 lanes of a half hit 32 banks
-constexpr int kRec = 8;                 // floats per pixel record: n, R, linear pixel index, pad
-constexpr int kMaxSplit = 64;
-constexpr int kSlots = 512;             // 256 CUs x 2 resident workgroups (236 registers: 2 waves per SIMD)
-constexpr int kMaxS = 1024, kMaxH = 4096, kMaxB = 4096;
+using namespace eml::sgemm;
+using eml::env::lobe;                   // the select form, shared with the prefilter
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kRec = 8;                 // floats per pixel record: n, R, linear pixel index, pad
+constexpr int kMaxS = 1024, kMaxH = 4096, kMaxB = 4096;
 
 // Row i of the S x S image: the inside pixels X^2 + Y^2 < S^2 (X = 2j + 1 - S, Y = S - 1 - 2i) are j0 .. S - 1 - j0
 __host__ __device__ inline bool inside_px(int S, int i, int j) {
@@ -54,42 +45,11 @@ inline long inside_count(int S) {
   return P;
 }
 
-struct Plan {
-  long T, P;
-  int nchunks, per, splits, rowgroups, colgroups;
-};
-// the k split is a function of (H, W, S) alone: an image's summation order must not depend on the batch
-inline Plan make_plan(int B, int H, int W, int S) {
-  Plan pl;
-  pl.T = (long)H * W;
-  pl.P = inside_count(S);
-  pl.nchunks = (int)((pl.T + kKC - 1) / kKC);
-  pl.rowgroups = (int)((pl.P + kRowsWG - 1) / kRowsWG);
-  pl.colgroups = (3 * B + kColsWG - 1) / kColsWG;
-  int want = kSlots / pl.rowgroups;                  // one column group's workgroups fit the part at once: no second round
-  if (want > kMaxSplit) want = kMaxSplit;
-  if (want > pl.nchunks) want = pl.nchunks;
-  if (want < 1) want = 1;
-  pl.per = (pl.nchunks + want - 1) / want;
-  pl.splits = (pl.nchunks + pl.per - 1) / pl.per;
-  return pl;
-}
 inline bool size_ok(int B, int H, int W, int S) {
   return B >= 0 && B <= kMaxB && H >= 1 && H <= kMaxH && W == 2 * H && S >= 2 && S <= kMaxS;
 }
 
 // ------------------------------------------------------------------------------------------------ tables
-// texel (h, w): omega and dOmega in f64, rounded once
-__global__ __launch_bounds__(kThreads) void texel_table_kernel(int H, int W, float4* __restrict__ tab) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
-  if (t >= H * W) return;
-  const int h = t / W, w = t - h * W;
-  const double th = ((double)h + 0.5) * kPi / (double)H, ph = ((double)w + 0.5) * (2.0 * kPi) / (double)W;
-  const double st = sin(th);
-  tab[t] = make_float4((float)(st * cos(ph)), (float)(st * sin(ph)), (float)cos(th),
-                       (float)(st * (kPi / (double)H) * (2.0 * kPi / (double)W)));
-}
-
 // n and R of pixel (i, j) in f64: r = (-s, c, 0), u = (0, 0, 1), v = (-c, -s, 0) with (c, s) = (cos, sin) of the azimuth
 __device__ __forceinline__ void pixel_frame(int S, int i, int j, double c, double s, double* n, double* R) {
   const double px = (double)(2 * j + 1 - S) / (double)S, py = (double)(S - 1 - 2 * i) / (double)S;
@@ -132,111 +92,72 @@ __global__ __launch_bounds__(kThreads) void pixel_list_kernel(int S, double c, d
 }
 
 // ------------------------------------------------------------------------------------------------ integrals
-// x^m for x >= 0 (x = 0: 1 when m == 0, as numpy's 0.0 ** 0)
-__device__ __forceinline__ float lobe(float x, float m) {
-  return x > 0.f ? exp2f(m * log2f(x)) : (m == 0.f ? 1.f : 0.f);
-}
-
-// grid (rowgroups, colgroups, splits).  part[split][material 0..1][pixel][column]
+// grid (rowgroups, colgroups, splits).  part[split][material 0..1][pixel][column].  Three column tiles under the guard
 template <bool DIFF, bool GLOSS>
 __global__ __launch_bounds__(kThreads) void integral_kernel(const float* __restrict__ pano, const float4* __restrict__ tab,
                                                             const float* __restrict__ rec, int P, int T, int N, int per,
                                                             int nchunks, float m, float* __restrict__ part) {
+  constexpr int kMats = (int)DIFF + (int)GLOSS;
   __shared__ float sp[kColsWG * kStride];
   __shared__ float4 st[kKC];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
-  const int p = blockIdx.x * kRowsWG + wave * 32 + r;
+  const Lanes ln = lanes();
+  const int tid = ln.tid;
   float nx = 0.f, ny = 0.f, nz = 0.f, Rx = 0.f, Ry = 0.f, Rz = 0.f;      // a row beyond P weighs 0 and is never stored
-  if (p < P) {
-    const float* q = rec + (size_t)p * kRec;
+  if (ln.row < P) {
+    const float* q = rec + (size_t)ln.row * kRec;
     nx = q[0], ny = q[1], nz = q[2], Rx = q[3], Ry = q[4], Rz = q[5];
   }
   const int col0 = blockIdx.y * kColsWG;
   const int ncols = N - col0 < kColsWG ? N - col0 : kColsWG;             // > 0 by the grid
-  f32x16 accd[3], accg[3];
+  f32x16 acc[kMats][3];                                                  // diffuse first
 #pragma unroll
-  for (int ct = 0; ct < 3; ++ct)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) accd[ct][e] = 0.f, accg[ct][e] = 0.f;
+  for (int i = 0; i < kMats; ++i) zero(acc[i]);
 
-  const int c_begin = blockIdx.z * per;
-  const int c_end = c_begin + per < nchunks ? c_begin + per : nchunks;
-  constexpr int kLoads = kColsWG * kKC / kThreads;                       // 24 values per thread and chunk
-  float pre[kLoads];
+  const ChunkRange cr = split_chunks(per, nchunks);
+  float pre[kColsWG * kKC / kThreads];
   float4 pre_t;
-  // chunk c -> registers; a wave reads 64 consecutive texels of one plane
-  auto fetch = [&](int c) {
-    const int k0 = c * kKC;
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid, cl = idx >> 6, k = k0 + (idx & (kKC - 1));
-      pre[e] = (cl < ncols && k < T) ? pano[(size_t)(col0 + cl) * (size_t)T + k] : 0.f;
-    }
+  // a wave reads 64 consecutive texels of one plane
+  auto fetch = [&](int step) {
+    const int k0 = (cr.begin + step) * kKC;
+    for_each_load<3>(tid, [&](int e, int cl, int k) {
+      pre[e] = (cl < ncols && k0 + k < T) ? pano[(size_t)(col0 + cl) * (size_t)T + k0 + k] : 0.f;
+    });
     pre_t = (tid < kKC && k0 + tid < T) ? tab[k0 + tid] : make_float4(0.f, 0.f, 0.f, 0.f);
   };
-  if (c_begin < c_end) fetch(c_begin);
-  for (int c = c_begin; c < c_end; ++c) {
-    __syncthreads();                                                     // the previous chunk has been read
-#pragma unroll
-    for (int e = 0; e < kLoads; ++e) {
-      const int idx = e * kThreads + tid;
-      sp[(idx >> 6) * kStride + (idx & (kKC - 1))] = pre[e];
-    }
+  auto stage = [&]() {
+    stage_plane<3>(sp, pre, tid);
     if (tid < kKC) st[tid] = pre_t;
-    __syncthreads();
-    if (c + 1 < c_end) fetch(c + 1);                                     // in flight while this chunk is computed
-#pragma unroll 2
-    for (int kk = 0; kk < kKC; kk += 2) {
-      const float4 t = st[kk + half];
-      float wd = 0.f, wg = 0.f;
-      if (DIFF) wd = fmaxf(fmaf(nx, t.x, fmaf(ny, t.y, nz * t.z)), 0.f) * t.w;
-      if (GLOSS) wg = lobe(fmaf(Rx, t.x, fmaf(Ry, t.y, Rz * t.z)), m) * t.w;
-#pragma unroll
-      for (int ct = 0; ct < 3; ++ct) {
-        if (ct * 32 < ncols) {                                           // wave-uniform
-          const float b = sp[(ct * 32 + r) * kStride + kk + half];
-          if (DIFF) accd[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wd, b, accd[ct], 0, 0, 0);
-          if (GLOSS) accg[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wg, b, accg[ct], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // C/D of the 32x32 tile: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+  };
+  auto weight = [&](int k, float (&w)[kMats]) {
+    const float4 t = st[k];
+    if (DIFF) w[0] = fmaxf(fmaf(nx, t.x, fmaf(ny, t.y, nz * t.z)), 0.f) * t.w;
+    if (GLOSS) w[kMats - 1] = lobe(fmaf(Rx, t.x, fmaf(Ry, t.y, Rz * t.z)), m) * t.w;
+  };
+  pipeline(cr.end - cr.begin, fetch, stage, [&]() { chunk_mac<3, kMats, true, true, true>(sp, ncols, ln, weight, acc); });
+
   const size_t plane = (size_t)P * (size_t)N;
   float* pd = part + (size_t)blockIdx.z * 2 * plane;
-#pragma unroll
-  for (int ct = 0; ct < 3; ++ct) {
-    const int cl = ct * 32 + r;
-    if (cl >= ncols) continue;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = blockIdx.x * kRowsWG + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-      if (row >= P) continue;
-      const size_t o = (size_t)row * N + col0 + cl;
-      if (DIFF) pd[o] = accd[ct][e];
-      if (GLOSS) pd[plane + o] = accg[ct][e];
-    }
-  }
+  for_each_c<3>(ln, [&](int ct, int e, int i, int j) {
+    const int row = ln.row0 + i, cl = ct * 32 + j;
+    if (cl >= ncols || row >= P) return;
+    const size_t o = (size_t)row * N + col0 + cl;
+    if (DIFF) pd[o] = acc[0][ct][e];
+    if (GLOSS) pd[plane + o] = acc[kMats - 1][ct][e];
+  });
 }
 
-// out[b][slot][ch][pixel] = scale * sum over the splits, in split order.  grid (ceil(P N / 256), 2): y = material
-__global__ __launch_bounds__(kThreads) void integral_reduce_kernel(const float* __restrict__ part,
-                                                                   const float* __restrict__ rec, int P, int N, int splits,
-                                                                   int S, int M, int slot_d, int slot_g, float scale_d,
-                                                                   float scale_g, float* __restrict__ out) {
-  const int mat = blockIdx.y;
-  const int slot = mat == 0 ? slot_d : slot_g;
-  if (slot < 0) return;
-  const size_t plane = (size_t)P * (size_t)N;
-  const size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (e >= plane) return;
-  const int p = (int)(e / N), col = (int)(e - (size_t)p * N);
-  float s = 0.f;
-  for (int k = 0; k < splits; ++k) s += part[((size_t)k * 2 + mat) * plane + e];
-  const int pix = __float_as_int(rec[(size_t)p * kRec + 6]);
-  const int b = col / 3, ch = col - 3 * b;
-  out[(((size_t)b * M + slot) * 3 + ch) * (size_t)S * S + pix] = s * (mat == 0 ? scale_d : scale_g);
-}
+// out[b][slot][ch][pixel] = scale * the sum over the splits; mat 0: diffuse, 1: glossy
+struct StoreRender {
+  const float* rec;
+  int S, M, slot_d, slot_g;
+  float scale_d, scale_g;
+  float* out;
+  __device__ void operator()(int p, int col, int mat, float s) const {
+    const int pix = __float_as_int(rec[(size_t)p * kRec + 6]);
+    const int b = col / 3, ch = col - 3 * b;
+    out[(((size_t)b * M + (mat == 0 ? slot_d : slot_g)) * 3 + ch) * (size_t)S * S + pix] = s * (mat == 0 ? scale_d : scale_g);
+  }
+};
 
 // ------------------------------------------------------------------------------------------------ mirror
 __device__ __forceinline__ float lerp_f32(float a, float b, float t) {
@@ -325,6 +246,9 @@ __global__ __launch_bounds__(kThreads) void mirror_taps_kernel(int H, int W, int
 // l & 31, same pixel): the C tile's lane & 31 is the texel, so a store row is 32 consecutive floats of one image plane.
 // Both materials go into ONE accumulator set.  The mirror's taps on a texel (CSR, sorted by texel) are added in CSR order
 // after the integrals by the lane that holds the texel.  grid (ceil(T / 128), colgroups)
+// This kernel keeps its own chunk loop beside sphere_gemm.h's: written through the shared pipeline and multiply-accumulate it
+// lost the register allocation of the tap loop below (205 -> 176 VGPRs, the 48 tap addresses recomputed per tap) and the
+// backward with taps went 0.78 -> 0.90 ms.
 template <bool DIFF, bool GLOSS>
 __global__ __launch_bounds__(kThreads) void adjoint_kernel(const float* __restrict__ g, const float4* __restrict__ tab,
                                                            const float* __restrict__ rec, int P, int T, int N, int SS, int M,
@@ -523,8 +447,8 @@ void launch_integral(dim3 grid, hipStream_t s, const float* pano, const float4* 
 
 extern "C" size_t eml_sphere_render_work_floats(int B, int H, int W, int S) {
   if (!size_ok(B, H, W, S) || B == 0) return 0;
-  const Plan pl = make_plan(B, H, W, S);
-  return 4 * (size_t)pl.T + (size_t)kRec * pl.P + (size_t)pl.splits * 2 * pl.P * 3 * (size_t)B;
+  const size_t T = (size_t)H * W, P = inside_count(S);
+  return 4 * T + (size_t)kRec * P + (size_t)make_split_plan(P, T).splits * 2 * P * 3 * (size_t)B;
 }
 
 extern "C" int eml_sphere_render_f32(const float* pano, int B, int H, int W, int S, double view_azimuth_deg,
@@ -540,8 +464,8 @@ extern "C" int eml_sphere_render_f32(const float* pano, int B, int H, int W, int
     return eml::fail(EML_EINVAL, "eml_sphere_render_f32: grid limits: 0 <= B <= %d, H <= %d, S <= %d", kMaxB, kMaxH, kMaxS);
   if (B == 0) return EML_OK;
   hipStream_t s = (hipStream_t)stream;
-  const Plan pl = make_plan(B, H, W, S);
-  const int P = (int)pl.P, T = (int)pl.T, N = 3 * B;
+  const int P = (int)inside_count(S), T = H * W, N = 3 * B;
+  const SplitPlan pl = make_split_plan(P, T);               // of (H, W, S) alone: not of the batch
   const bool diff = materials_mask & EML_SPHERE_DIFFUSE, gloss = materials_mask & EML_SPHERE_GLOSSY,
              mirror = materials_mask & EML_SPHERE_MIRROR;
   const int M = (int)diff + (int)gloss + (int)mirror;
@@ -556,18 +480,16 @@ extern "C" int eml_sphere_render_f32(const float* pano, int B, int H, int W, int
   if (e != hipSuccess) return eml::fail(EML_ELAUNCH, "eml_sphere_render_f32(zero): %s", hipGetErrorString(e));
   hipLaunchKernelGGL(pixel_list_kernel, dim3(1), dim3(kThreads), 0, s, S, c, sn, rec);
   if (diff || gloss) {
-    hipLaunchKernelGGL(texel_table_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, W, tab);
-    const dim3 grid(pl.rowgroups, pl.colgroups, pl.splits);
+    hipLaunchKernelGGL(grid_table_kernel<>, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, tab);
+    const dim3 grid(pl.rowgroups, (N + kColsWG - 1) / kColsWG, pl.splits);
     const float m = (float)phong_m;
     if (diff && gloss) launch_integral<true, true>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
     else if (diff) launch_integral<true, false>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
     else launch_integral<false, true>(grid, s, pano, tab, rec, P, T, N, pl.per, pl.nchunks, m, part);
     int rc = eml::check_launch("eml_sphere_render_f32(integral)");
     if (rc) return rc;
-    const size_t plane = (size_t)P * N;
-    hipLaunchKernelGGL(integral_reduce_kernel, dim3((unsigned)((plane + kThreads - 1) / kThreads), 2), dim3(kThreads), 0, s,
-                       (const float*)part, (const float*)rec, P, N, pl.splits, S, M, slot_d, slot_g, (float)(1.0 / kPi),
-                       (float)((phong_m + 1.0) / (2.0 * kPi)), out);
+    launch_split_reduce(s, part, P, N, pl.splits, 2, diff ? 0 : 1, (int)diff + (int)gloss,
+                        StoreRender{rec, S, M, slot_d, slot_g, (float)(1.0 / kPi), (float)((phong_m + 1.0) / (2.0 * kPi)), out});
   }
   if (mirror)
     hipLaunchKernelGGL(mirror_kernel, dim3((P + kThreads - 1) / kThreads, B), dim3(kThreads), 0, s, pano, (const float*)rec, P,
@@ -609,7 +531,7 @@ extern "C" int eml_sphere_render_bwd_f32(const float* grad_out, int B, int H, in
   float* rec = work + 4 * (size_t)T;
   const double az = view_azimuth_deg * (kPi / 180.0), c = cos(az), sn = sin(az);
   hipLaunchKernelGGL(pixel_list_kernel, dim3(1), dim3(kThreads), 0, s, S, c, sn, rec);
-  hipLaunchKernelGGL(texel_table_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, W, tab);
+  hipLaunchKernelGGL(grid_table_kernel<>, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, s, H, tab);
   int rc = eml::check_launch("eml_sphere_render_bwd_f32(tables)");
   if (rc) return rc;
   const dim3 grid((T + kRowsWG - 1) / kRowsWG, (N + kColsWG - 1) / kColsWG);
