@@ -96,12 +96,25 @@ class PickleParameterDataset(Dataset):
 
 class PanoramaDataset(Dataset):
     """``<root>/*.npy`` HDR panoramas ``(H, W, 3)`` (equirect, linear radiance), returned as float32 tensors with their
-    names.  EXR input stays out of scope: convert offline."""
+    names.  EXR input stays out of scope: convert offline.
 
-    def __init__(self, root):
+    ``depth_dir``: every item also has ``depth_pano`` ``(H, W)`` float32 from ``<depth_dir>/<name>.npy``, the distance from the
+    viewpoint to the scene along each pixel's direction (what ``PanoramaBatcher(depth_panos=...)`` takes).  A panorama
+    without a depth file is a ``FileNotFoundError`` at construction; a depth of another shape, or with a value that is not
+    finite or not > 0, is a ``ValueError`` naming the file when the item is read."""
+
+    def __init__(self, root, depth_dir=None):
         self.items = sorted(glob.glob(os.path.join(root, "*.npy")))
         if not self.items:
             raise FileNotFoundError("no *.npy under %s" % root)
+        self.depth_dir = depth_dir
+        if depth_dir is not None:
+            for path in self.items:
+                if not os.path.isfile(self.depth_path(path)):
+                    raise FileNotFoundError("%s has no depth panorama %s" % (path, self.depth_path(path)))
+
+    def depth_path(self, path):
+        return os.path.join(self.depth_dir, os.path.basename(path))
 
     def __len__(self):
         return len(self.items)
@@ -111,8 +124,19 @@ class PanoramaDataset(Dataset):
         pano = np.load(path)
         if pano.ndim != 3 or pano.shape[2] != 3:
             raise ValueError("%s: expected a (H, W, 3) panorama, got %s" % (path, pano.shape))
-        return {"pano": torch.from_numpy(np.ascontiguousarray(pano, dtype=np.float32)),
+        item = {"pano": torch.from_numpy(np.ascontiguousarray(pano, dtype=np.float32)),
                 "name": os.path.basename(path)[:-len(".npy")]}
+        if self.depth_dir is not None:
+            dpath = self.depth_path(path)
+            depth = np.load(dpath)
+            if depth.shape != pano.shape[:2]:
+                raise ValueError("%s: expected a depth panorama of shape %s like %s, got %s"
+                                 % (dpath, pano.shape[:2], path, depth.shape))
+            depth = np.ascontiguousarray(depth, dtype=np.float32)
+            if not (np.isfinite(depth).all() and (depth > 0).all()):
+                raise ValueError("%s: every depth must be finite and > 0" % dpath)
+            item["depth_pano"] = torch.from_numpy(depth)
+        return item
 
 
 def add_warp_option(ap):
@@ -120,7 +144,8 @@ def add_warp_option(ap):
     ap.add_argument("--warp_move", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                     help="--pano_dir: derive the targets from the panorama warped to a position `move` sphere radii along the "
                          "view axis (negative: toward what the crop shows), one move per sample drawn uniformly in [LO, HI) "
-                         "(PanoramaBatcher(move_range=...)); default: the camera's own position")
+                         "(PanoramaBatcher(move_range=...)); default: the camera's own position.  With --depth_dir (the "
+                         "regression trainer) the warp follows the scene's depth and LO, HI are in the units of the depth")
     return ap
 
 
@@ -240,9 +265,29 @@ class PanoramaBatcher:
                 "rgb_ratio": para["rgb_ratio"].float(),
                 "ambient": para["ambient"].float() * alpha[:, None] / (128 * 256)}
 
-    def __call__(self, panos, deg=None, fov_deg=None, warp=None):
+    def small_depth(self, panos, depth_panos, deg):
+        """The depth panoramas ``(B, H, W)`` rotated and area-resized to 128 x 256 like the panoramas, ``(B, 128, 256)``: the
+        same resize entry on a three-channel view of the depth (a copy of 3 H W floats per sample; no second resize kernel)."""
+        if not isinstance(depth_panos, torch.Tensor) or depth_panos.shape != panos.shape[:3]:
+            raise ValueError("depth_panos: expected %s like the panoramas, got %s"
+                             % (tuple(panos.shape[:3]), tuple(getattr(depth_panos, "shape", ()))))
+        return self.small(depth_panos.unsqueeze(-1).expand(-1, -1, -1, 3).contiguous(), deg)[..., 0].contiguous()
+
+    def __call__(self, panos, deg=None, fov_deg=None, warp=None, depth_panos=None):
+        """``depth_panos`` ``(B, H, W)`` float32, the scene's distance along each pixel of ``panos``: the result gains ``depth``
+        ``(B, anchors)`` float32, the per-anchor depth GMLight's loss takes (``extract_mesh.anchor_depth``), and a warp becomes
+        the parallax-correct one (``PanoramaHandler.warp_panorama_depth``) with ``move`` in the units of the depth: targets and
+        depth are then those of the new position.  Without it the calls made and every output are what they were."""
         deg, fov = self.view(panos, deg, fov_deg)
         warp = self.warp_of(panos, warp)
         crop, alpha = self.tone(self.crop(panos, deg, fov))
-        para, _ = self.mesh.compute(self.warped(self.small(panos, deg), warp))
-        return {"crop": crop, **self.targets(para, alpha), "alpha": alpha}
+        small = self.small(panos, deg)
+        if depth_panos is None:
+            para, _ = self.mesh.compute(self.warped(small, warp))
+            return {"crop": crop, **self.targets(para, alpha), "alpha": alpha}
+        depth = self.small_depth(panos, depth_panos, deg)
+        if warp is not None:
+            from .util import PanoramaHandler
+            small, depth = PanoramaHandler.warp_panorama_depth(small, depth, None, theta=warp[0], phi=warp[1], move=warp[2])
+        para, _ = self.mesh.compute(small)
+        return {"crop": crop, **self.targets(para, alpha), "depth": self.mesh.anchor_depth(depth).float(), "alpha": alpha}

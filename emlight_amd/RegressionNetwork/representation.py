@@ -31,6 +31,25 @@ class extract_mesh:
         self.csr_ptr[1:] = torch.cumsum(torch.bincount(self.idx.long(), minlength=ln), 0).to(torch.int32)
         self.lum = torch.tensor([0.3, 0.59, 0.11], dtype=torch.float64, device=dev)   # made once: compute() only enqueues
 
+    def anchor_depth(self, depth):
+        """The per-anchor scene depth that GMLight's loss takes (the ``depth`` of the reference's pickles, ``data.py:75``, which
+        ``gmloss/utils.py:63-73`` scales the anchors by) from a depth panorama on the mesh's grid: ``(H, W)`` or ``(B, H, W)``
+        float32 -> ``(N,)`` or ``(B, N)`` float64, the steradian-weighted mean over each anchor's Voronoi cell.  A pixel that
+        is not finite is left out; a cell with nothing left gives NaN."""
+        if not isinstance(depth, torch.Tensor) or depth.dim() not in (2, 3):
+            raise ValueError("depth: expected a (H, W) or (B, H, W) tensor, got %s" % (tuple(getattr(depth, "shape", ())),))
+        single = depth.dim() == 2
+        d = _lib.require_gpu_tensor(depth.unsqueeze(0) if single else depth, "depth")
+        B, H, W = d.shape
+        if (H, W) != (self.h, self.w):
+            raise ValueError("expected depth of shape (..., %d, %d), got %s" % (self.h, self.w, tuple(depth.shape)))
+        out = torch.empty(B, self.ln, dtype=torch.float64, device=d.device)
+        if B > 0:
+            _lib.check(_lib.lib().eml_gt_anchor_depth_f64(_lib.ptr(d), _lib.ptr(self.csr_ptr), _lib.ptr(self.csr_pix), B, H, W,
+                                                          self.ln, _lib.ptr(out), _lib.current_stream()),
+                       "eml_gt_anchor_depth_f64")
+        return out[0] if single else out
+
     def compute(self, hdr):
         single = hdr.dim() == 3
         x = _lib.require_gpu_tensor(hdr.unsqueeze(0) if single else hdr, "hdr")

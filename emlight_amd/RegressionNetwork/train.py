@@ -6,6 +6,7 @@ torchrun-aware, same optimiser, loss weights, print/visualise/checkpoint cadence
     torchrun --nproc-per-node 8 -m emlight_amd.RegressionNetwork.train --synthetic
     python -m emlight_amd.RegressionNetwork.train --pano_dir DIR --fov 60 [--warp_move -0.6 0]      # crops and targets made on the GPU per step
     python -m emlight_amd.RegressionNetwork.train --synthetic --geometry --anchors 128                # GMLight's loss, one scene depth per sample
+    python -m emlight_amd.RegressionNetwork.train --geometry --pano_dir DIR --depth_dir DIR2 [--warp_move -0.8 0]   # its depths from depth panoramas
 """
 import argparse
 import os
@@ -66,7 +67,11 @@ def build_parser():
     ap.add_argument("--geometry", action="store_true",
                     help="GMLight's geometric mover's loss (gmloss.SamplesLoss): the Sinkhorn ground cost of every sample from "
                          "its scene's per-anchor depth, which the dataset must return (--synthetic draws one; --train_dir "
-                         "pickles must hold 'depth'); not with --pano_dir, which has no depth panoramas")
+                         "pickles must hold 'depth'; --pano_dir needs --depth_dir, alone it has no depth panoramas)")
+    ap.add_argument("--depth_dir", default=None,
+                    help="--pano_dir: directory of <name>.npy depth panoramas (H, W) float32, one per panorama, the distance to "
+                         "the scene along each pixel: every batch gains the per-anchor depth that --geometry needs, and "
+                         "--warp_move becomes the parallax-correct warp with LO, HI in the units of the depth")
     data.add_warp_option(ap)
     return ap
 
@@ -75,9 +80,12 @@ def parse_args(argv=None):
     """``build_parser().parse_args`` plus the combinations that are refused at parsing."""
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.geometry and args.pano_dir:
-        ap.error("--geometry needs a per-anchor depth for every sample and --pano_dir has no depth panoramas to derive it "
-                 "from: use --synthetic or a --train_dir whose pickles hold 'depth'")
+    if args.depth_dir and not args.pano_dir:
+        ap.error("--depth_dir holds the depth panoramas of the --pano_dir panoramas; without --pano_dir there is nothing they "
+                 "belong to")
+    if args.geometry and args.pano_dir and not args.depth_dir:
+        ap.error("--geometry needs a per-anchor depth for every sample and --pano_dir alone has no depth panoramas to derive "
+                 "it from: add --depth_dir, or use --synthetic or a --train_dir whose pickles hold 'depth'")
     return args
 
 
@@ -108,7 +116,7 @@ def main(argv=None):
             print("load trained model")
     batcher = make_batcher(args, device)
     if batcher is not None:
-        ds = data.PanoramaDataset(args.pano_dir)
+        ds = data.PanoramaDataset(args.pano_dir, depth_dir=args.depth_dir)
     elif args.synthetic or not args.train_dir:
         ds = data.SyntheticParameterDataset(anchors=args.anchors, crop_hw=tuple(args.crop_hw), with_depth=args.geometry)
     else:
@@ -128,7 +136,8 @@ def main(argv=None):
             print("{} optim: {}".format(epoch, tr.optimizer.param_groups[0]["lr"]))
         for i, para in enumerate(loader):
             if batcher is not None:
-                batch = batcher(para["pano"].to(device, non_blocking=True))
+                depth = para["depth_pano"].to(device, non_blocking=True) if "depth_pano" in para else None
+                batch = batcher(para["pano"].to(device, non_blocking=True), depth_panos=depth)
             else:
                 batch = {k: v.to(device, non_blocking=True) for k, v in para.items() if k != "name"}
             loss, terms = tr.step(batch)

@@ -4,7 +4,8 @@
 ``sphere_points`` (``util.py:286-299``) is the small host helper the kept entry points need.
 ``PanoramaHandler`` (``util.py:69-185``: crop, rotate, resize) and ``TonemapHDR`` (``util.py:36-66``) run on device
 tensors, batched (csrc/pano_prep.hip); ``PanoramaHandler.warp_panorama`` is the panorama warp of ``GenProjector/util.py:279-343``
-(csrc/pano_warp.hip, gradients: csrc/pano_warp_bwd.hip); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
+(csrc/pano_warp.hip, gradients: csrc/pano_warp_bwd.hip), ``PanoramaHandler.warp_panorama_depth`` the same warp with the scene
+where its depth panorama puts it (csrc/pano_warp_depth.hip, forward only); ``TonemapHDR`` keeps the reference's numpy form for numpy input.
 EXR/vtk/cv2 I/O is out of scope.
 """
 import functools
@@ -148,6 +149,39 @@ def _per_sample(value, B, name):
             raise ValueError("%s: expected one value per sample, shape (%d,), got %s" % (name, B, tuple(value.shape)))
         return 0.0, value.to(torch.float64).contiguous()
     return float(value), None
+
+
+def _warp_arguments(what, bhw, device, new_shape, theta, phi, move):
+    """The argument handling that ``warp_panorama`` and ``warp_panorama_depth`` share: the output size from ``new_shape``
+    (``(w, h)``, an int ``h`` meaning ``(2h, h)``, ``None`` for the source's) and the three parameters, each a Python number or
+    a ``(B,)`` device tensor.  Returns ``(h, w, params, vals)``: ``params`` is the packed ``(B, 3)`` float64 device array if any
+    parameter is a tensor (then ``vals`` is zeros), else ``None`` and ``vals`` the three finite by-value numbers."""
+    B, H, W = bhw
+    if new_shape is None:
+        w, h = W, H
+    elif isinstance(new_shape, tuple) and len(new_shape) == 2:
+        w, h = int(new_shape[0]), int(new_shape[1])
+    elif isinstance(new_shape, int):
+        w, h = 2 * new_shape, new_shape
+    else:
+        raise ValueError("new_shape must be (w, h), an int h or None, got %r" % (new_shape,))
+    if h < 1 or w < 1 or H < 1 or W < 1:
+        raise ValueError("%s: empty image, %d x %d -> %d x %d" % (what, H, W, h, w))
+    vals = [_per_sample(v, B, n) for v, n in ((theta, "theta"), (phi, "phi"), (move, "move"))]
+    params = None
+    if any(t is not None for _, t in vals):
+        params = torch.stack([t if t is not None else torch.full((B,), v, dtype=torch.float64, device=device)
+                              for v, t in vals], dim=1).contiguous()
+        vals = [(0.0, None)] * 3
+    elif not all(np.isfinite(v) for v, _ in vals):
+        raise ValueError("%s: theta, phi and move must be finite, got %r" % (what, [v for v, _ in vals]))
+    return h, w, params, tuple(v for v, _ in vals)
+
+
+def _forward_only(t, name, what):
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("%s requires grad: %s is forward only; pass %s.detach()" % (name, what, name))
+    return t
 
 
 def _warp_forward(x, params, vals, hw, return_coords):
@@ -354,26 +388,7 @@ class PanoramaHandler(object):
         differentiates in its right-hand cell, a pixel within 0.06 degrees of the source's pole adds nothing to the parameters'
         gradients.  Otherwise the call is the one forward launch, bit for bit."""
         x, single = PanoramaHandler._batched(hdr_img, "hdr_img")
-        B, H, W, _ = x.shape
-        if new_shape is None:
-            w, h = W, H
-        elif isinstance(new_shape, tuple) and len(new_shape) == 2:
-            w, h = int(new_shape[0]), int(new_shape[1])
-        elif isinstance(new_shape, int):
-            w, h = 2 * new_shape, new_shape
-        else:
-            raise ValueError("new_shape must be (w, h), an int h or None, got %r" % (new_shape,))
-        if h < 1 or w < 1 or H < 1 or W < 1:
-            raise ValueError("warp_panorama: empty image, %d x %d -> %d x %d" % (H, W, h, w))
-        vals = [_per_sample(v, B, n) for v, n in ((theta, "theta"), (phi, "phi"), (move, "move"))]
-        params = None
-        if any(t is not None for _, t in vals):
-            params = torch.stack([t if t is not None else torch.full((B,), v, dtype=torch.float64, device=x.device)
-                                  for v, t in vals], dim=1).contiguous()
-            vals = [(0.0, None)] * 3
-        elif not all(np.isfinite(v) for v, _ in vals):
-            raise ValueError("warp_panorama: theta, phi and move must be finite, got %r" % ([v for v, _ in vals],))
-        vals = tuple(v for v, _ in vals)
+        h, w, params, vals = _warp_arguments("warp_panorama", x.shape[:3], x.device, new_shape, theta, phi, move)
         if torch.is_grad_enabled() and (x.requires_grad or (params is not None and params.requires_grad)):
             res = _WarpPanorama.apply(x, params, vals, (h, w), bool(return_coords))
             out, coords = res if return_coords else (res, None)
@@ -383,6 +398,55 @@ class PanoramaHandler(object):
             out = out[0]
             coords = coords[0] if return_coords else None
         return (out, coords) if return_coords else out
+
+    @staticmethod
+    def warp_panorama_depth(hdr_img, depth, new_shape=None, theta=0.0, phi=0.0, move=0.0, steps=32, bisections=24,
+                            return_hit=False):
+        """``warp_panorama`` with the scene's own geometry (``eml_pano_warp_depth_f32``): the panorama AND its depth as seen
+        after rotating the frame by ``theta``, ``phi`` (degrees, as ``warp_panorama``) and stepping ``move`` along the rotated -z
+        axis, in the UNITS OF ``depth``.  ``depth`` ``(H, W)`` or ``(B, H, W)`` float32 is the distance from the viewpoint to
+        the scene along each pixel's direction, finite and > 0.  Every output pixel's ray from the new viewpoint is marched
+        (``steps`` equal steps over the interval that must hold the surface) to the first crossing of the depth map, which
+        ``bisections`` halvings refine: a light that is close grows and shifts more than one that is far.  Returns
+        ``(pano, depth)`` -- ``(B, h, w, 3)`` and ``(B, h, w)`` float32, without the batch axis for a single image; ``pano`` is
+        ``None`` for ``hdr_img=None`` (depth only) -- and with ``return_hit`` also the float64 ``(B, h, w, 3)`` array of
+        ``(t, row, col)``: the distance along the ray and the source position the pixel was sampled at.  Sampling is bilinear
+        with wrapping columns and CLAMPED rows.  ``new_shape`` and the number-or-``(B,)``-tensor parameters are
+        ``warp_panorama``'s.  A sample whose depth has a value that is not finite or not > 0, whose parameters are not finite,
+        or whose new viewpoint lies on or behind the surface comes out as NaN, all of it.  The depth map is treated as one
+        connected surface: regions the source viewpoint never saw are not filled, the surface is stretched across them.
+        Forward only: an input that requires grad raises ``ValueError``."""
+        what = "warp_panorama_depth"
+        for t, name in ((hdr_img, "hdr_img"), (depth, "depth"), (theta, "theta"), (phi, "phi"), (move, "move")):
+            _forward_only(t, name, what)
+        if not isinstance(depth, torch.Tensor) or depth.dim() not in (2, 3):
+            raise ValueError("depth: expected a (H, W) or (B, H, W) tensor, got %s"
+                             % (tuple(getattr(depth, "shape", ())) or type(depth),))
+        single = depth.dim() == 2
+        d = _lib.require_gpu_tensor(depth.unsqueeze(0) if single else depth, "depth")
+        B, H, W = d.shape
+        x = None
+        if hdr_img is not None:
+            x, x_single = PanoramaHandler._batched(hdr_img, "hdr_img")
+            if x_single != single or x.shape != (B, H, W, 3):
+                raise ValueError("hdr_img %s and depth %s do not match" % (tuple(hdr_img.shape), tuple(depth.shape)))
+        steps, bisections = int(steps), int(bisections)
+        if not 1 <= steps <= 1024 or not 0 <= bisections <= 60:
+            raise ValueError("%s: steps in 1..1024 and bisections in 0..60, got %r, %r" % (what, steps, bisections))
+        h, w, params, vals = _warp_arguments(what, (B, H, W), d.device, new_shape, theta, phi, move)
+        out = torch.empty(B, h, w, 3, dtype=torch.float32, device=d.device) if x is not None else None
+        out_d = torch.empty(B, h, w, dtype=torch.float32, device=d.device)
+        hit = torch.empty(B, h, w, 3, dtype=torch.float64, device=d.device) if return_hit else None
+        if B > 0:
+            L = _lib.lib()
+            work = torch.empty(max(1, L.eml_pano_warp_depth_work_floats(B, H, W)), dtype=torch.float32, device=d.device)
+            _lib.check(L.eml_pano_warp_depth_f32(_lib.ptr(x), _lib.ptr(d), B, H, W, h, w, vals[0], vals[1], vals[2],
+                                                 _lib.ptr(params), steps, bisections, _lib.ptr(out), _lib.ptr(out_d),
+                                                 _lib.ptr(hit), _lib.ptr(work), _lib.current_stream()),
+                       "eml_pano_warp_depth_f32")
+        if single:
+            out, out_d, hit = (None if out is None else out[0]), out_d[0], (None if hit is None else hit[0])
+        return (out, out_d, hit) if return_hit else (out, out_d)
 
 
 def tonemap_raw(img, gamma=2.4, percentile=50, max_mapping=0.5, clip=True, alpha=None, use_gamma=True, apply=True):

@@ -274,6 +274,11 @@ EXT_SIGNATURES = {
                                          _f32p, _f32p, _f32p, _f32p, _int, _int, _int, ctypes.c_double, ctypes.c_double,
                                          _f32p, _f32p, ctypes.c_double, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
                                          _f32p, _stream]),
+    # depth panoramas: the parallax-correct warp (ray search against the depth map) and the per-anchor mean depth
+    "eml_pano_warp_depth_work_floats": (ctypes.c_size_t, [_int, _int, _int]),
+    "eml_pano_warp_depth_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_double, _f64p, _int, _int, _f32p, _f32p, _f64p, _f32p, _stream]),
+    "eml_gt_anchor_depth_f64": (_int, [_f32p, _i32p, _i32p, _int, _int, _int, _int, _f64p, _stream]),
 }
 
 _lock = threading.Lock()

@@ -5,6 +5,7 @@
 // over the anchors (each iteration masks the whole panorama); here: a one-off index map, one max-reduction and one
 // segmented (CSR) reduction per batch, all in f64, deterministic (fixed-order tree reductions, no atomics).
 #include "eml_common.h"
+#include "../../include/emlight_hip_ext.h"
 
 namespace {
 
@@ -115,7 +116,40 @@ __global__ __launch_bounds__(256) void gt_anchor_sums_kernel(const float* __rest
   }
 }
 
+// block (a, b): the steradian-weighted mean depth of anchor a's Voronoi cell, sum w D / sum w with w of `weighted`; a pixel
+// that is not finite has weight 0, a cell whose weights sum to 0 gives NaN (0 / 0)
+__global__ __launch_bounds__(256) void gt_anchor_depth_kernel(const float* __restrict__ depth, const int* __restrict__ cptr,
+                                                              const int* __restrict__ cpix, int H, int W, int N,
+                                                              double* __restrict__ out) {
+  __shared__ double red[256];
+  const int a = blockIdx.x, b = blockIdx.y;
+  const float* img = depth + (size_t)b * H * W;
+  double sd = 0.0, sw = 0.0;
+  for (int k = cptr[a] + threadIdx.x; k < cptr[a + 1]; k += 256) {
+    const int p = cpix[k];
+    const float d = img[p];
+    if (isfinite(d)) {
+      const double st = sin(((double)(p / W) + 0.5) / (double)H * kPi);
+      sd += st * (double)d;
+      sw += st;
+    }
+  }
+  sd = block_reduce(sd, red, false);
+  sw = block_reduce(sw, red, false);
+  if (threadIdx.x == 0) out[(size_t)b * N + a] = sd / sw;
+}
+
 }  // namespace
+
+extern "C" int eml_gt_anchor_depth_f64(const float* depth, const int* csr_ptr, const int* csr_pix, int B, int H, int W, int N,
+                                       double* out, eml_stream_t stream) {
+  if (!depth || !csr_ptr || !csr_pix || !out || B < 0 || H < 1 || W < 1 || N < 1 || B > 65535)
+    return eml::fail(EML_EINVAL, "eml_gt_anchor_depth_f64: bad arguments");
+  if (B == 0) return EML_OK;
+  hipLaunchKernelGGL(gt_anchor_depth_kernel, dim3(N, B), dim3(256), 0, (hipStream_t)stream, depth, csr_ptr, csr_pix, H, W, N,
+                     out);
+  return eml::check_launch("eml_gt_anchor_depth_f64");
+}
 
 extern "C" int eml_gt_anchor_index_i32(const double* anchors, int N, int H, int W, int* idx, eml_stream_t stream) {
   if (!anchors || !idx || N < 1 || H < 1 || W < 1) return eml::fail(EML_EINVAL, "eml_gt_anchor_index_i32: bad arguments");

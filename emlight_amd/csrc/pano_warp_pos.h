@@ -1,5 +1,6 @@
 // The source position of the panorama warp (GenProjector/util.py:279-343), shared by the forward (pano_warp.hip) and its
-// gradients (pano_warp_bwd.hip): both make their taps and weights from the SAME snapped f64 position, bit for bit.
+// gradients (pano_warp_bwd.hip): both make their taps and weights from the SAME snapped f64 position, bit for bit.  The
+// depth-aware warp (pano_warp_depth.hip) uses the two halves on their own: the frame of a pixel, the position of a point.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,10 +18,10 @@ __device__ __forceinline__ double snap_px(double x) {
   return fabs(x - n) < kSnap ? n : x;
 }
 
-// (row, col) of output pixel (i, j); false (and NaNs) where the position is not finite: |v| == 0, possible only at
-// |move| == 1, a NaN or infinite parameter, an overflow of move * m.
-__device__ __forceinline__ bool warp_position(int i, int j, int h, int w, int H, int W, double theta_deg, double phi_deg,
-                                              double move, double& row, double& col) {
+// The frame of output pixel (i, j): e = Rp Rt d(i, j) and m = Rp Rt (0, 0, -1), the two terms of the warp's v = e + move * m.
+// pano_warp_depth.hip walks the ray c + t e from the viewpoint c = move * m with the same e and m, bit for bit.
+__device__ __forceinline__ void warp_frame(int i, int j, int h, int w, double theta_deg, double phi_deg, double& E0, double& E1,
+                                           double& E2, double& m0, double& m1, double& m2) {
 #pragma clang fp contract(off)
   const double lat = (double)i * kPi / (double)h - kPi / 2.0, lon = (double)j * (2.0 * kPi) / (double)w;
   const double clat = cos(lat);
@@ -35,11 +36,18 @@ __device__ __forceinline__ bool warp_position(int i, int j, int h, int w, int H,
   const double r00 = c, r01 = -az * s, r02 = ay * s;
   const double r10 = az * s, r11 = c + ay * ay * k, r12 = ay * az * k;
   const double r20 = -ay * s, r21 = az * ay * k, r22 = c + az * az * k;
-  const double m0 = r00 * n0 + r01 * n1 + r02 * n2, m1 = r10 * n0 + r11 * n1 + r12 * n2, m2 = r20 * n0 + r21 * n1 + r22 * n2;
-  const double v0 = (r00 * e0 + r01 * e1 + r02 * e2) + move * m0;
-  const double v1 = (r10 * e0 + r11 * e1 + r12 * e2) + move * m1;
-  const double v2 = (r20 * e0 + r21 * e1 + r22 * e2) + move * m2;
-  const double len = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+  m0 = r00 * n0 + r01 * n1 + r02 * n2, m1 = r10 * n0 + r11 * n1 + r12 * n2, m2 = r20 * n0 + r21 * n1 + r22 * n2;
+  E0 = r00 * e0 + r01 * e1 + r02 * e2;
+  E1 = r10 * e0 + r11 * e1 + r12 * e2;
+  E2 = r20 * e0 + r21 * e1 + r22 * e2;
+}
+
+// (row, col) of the direction of v in an H x W source, and len = |v|; false (and NaN positions) where there is none:
+// |v| == 0 or not finite.
+__device__ __forceinline__ bool direction_position(double v0, double v1, double v2, int H, int W, double& row, double& col,
+                                                   double& len) {
+#pragma clang fp contract(off)
+  len = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
   row = col = __builtin_nan("");
   if (!(len > 0.0) || !isfinite(len)) return false;
   const double s0 = fmin(fmax(v0 / len, -1.0), 1.0), s1 = v1 / len, s2 = v2 / len;
@@ -52,6 +60,19 @@ __device__ __forceinline__ bool warp_position(int i, int j, int h, int w, int H,
   row = r;
   col = q;
   return true;
+}
+
+// (row, col) of output pixel (i, j); false (and NaNs) where the position is not finite: |v| == 0, possible only at
+// |move| == 1, a NaN or infinite parameter, an overflow of move * m.
+__device__ __forceinline__ bool warp_position(int i, int j, int h, int w, int H, int W, double theta_deg, double phi_deg,
+                                              double move, double& row, double& col) {
+#pragma clang fp contract(off)
+  double E0, E1, E2, m0, m1, m2, len;
+  warp_frame(i, j, h, w, theta_deg, phi_deg, E0, E1, E2, m0, m1, m2);
+  const double v0 = E0 + move * m0;
+  const double v1 = E1 + move * m1;
+  const double v2 = E2 + move * m2;
+  return direction_position(v0, v1, v2, H, W, row, col, len);
 }
 
 __device__ __forceinline__ int wrap_index(long long k, int n) {

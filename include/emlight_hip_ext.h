@@ -266,6 +266,51 @@ int eml_gbuffer_shade_bwd_f32(const float* grad_out, const float* pano, int H, c
                               float* dks, float* dkm, float* d_e_diffuse, float* d_e_phong, float* dpano, float* dshaded,
                               float* work, eml_stream_t stream);
 
+/* ---------------------------------------------------------------- depth panoramas: the parallax-correct warp
+ * GenProjector/util.py:279-343 gives the frame (`resize_exr`: the two rotations and the step along the rotated -z axis, as
+ * eml_pano_warp_f32 forms them, from the same code); gmloss/utils.py:63-73 (`geometric_points`) says what depth means: the
+ * distance from the viewpoint to the scene along a direction, the factor that scales a unit anchor.  The reference puts the
+ * whole scene on the unit sphere; here it stands where its depth panorama says, and `move` is in the units of `depth`.
+ * pano (B,H,W,3) f32 or NULL, depth (B,H,W) f32 -> out_pano (B,h,w,3) f32 or NULL, out_depth (B,h,w) f32 or NULL,
+ * hit (B,h,w,3) f64 = (t, row, col) or NULL.  For output pixel (i, j), all in f64 without contraction:
+ *   e = Rp Rt d(i, j),  m = Rp Rt (0,0,-1)  (eml_pano_warp_f32's two terms),  c = move * m,  P(t) = c + t e
+ *   position(P): s = P / |P|, row = (asin(clamp(s0)) + pi/2) / pi * H, col = (atan2(s1, -s2) mod 2 pi) / (2 pi) * W, with the
+ *     2^-28 px snap of eml_pano_warp_f32
+ *   D(P): bilinear sample of depth at position(P), f64 weights, products summed in the order 00, 01, 10, 11; columns wrap,
+ *     rows CLAMP: i0 = min(floor(row), H-1), i1 = min(i0+1, H-1) (eml_pano_warp_f32 blends the last row with row 0, the
+ *     opposite pole; for a distance that would mix ceiling and floor)
+ *   g(t) = |P(t)| - D(P(t)); a point with |P| == 0 counts as inside (g < 0)
+ * Pre-pass per sample (fixed-order reduction into `work`): dmin, dmax, and a flag for a pixel that is not finite or not > 0.
+ * A sample is INVALID when the flag is set, when one of its parameters is not finite, or when the viewpoint is on or outside
+ * the surface (|c| > 0 and |c| >= D(c)): every pixel of its outputs and of its hit entries is NaN; nothing else is touched.
+ * Bracket t_lo = max(0, dmin - |c|), t_hi = dmax + |c|; march t_k = t_lo + (t_hi - t_lo) k / steps, k = 1..steps, t_steps =
+ * t_hi exactly; the first k with g(t_k) >= 0 (k = steps when none) gives a = t_(k-1), b = t_k: the nearest surface.  Then
+ * `bisections` rounds mid = (a + b) / 2, g(mid) >= 0 ? b = mid : a = mid;  t = (a + b) / 2.  Fixed trip counts.
+ * out_depth = (float)t; (row, col) = position(P(t)); out_pano = the clamped-row bilinear sample of pano there, summed in f64
+ * and rounded once; a pixel whose P(t) has no position is NaN.  The depth map is treated as one connected surface: what the
+ * source viewpoint never saw is not filled.
+ * params_dev (B,3) f64 of (theta_deg, phi_deg, move) per sample, or NULL: the by-value three hold for the batch and must be
+ * finite.  No atomics; an image gives the same bits in any batch and with either kind of parameters.  One thread per
+ * output pixel, the depth gathered through the caches (a kernel that kept the map in LDS was slower: DESIGN.md section 26).
+ * work: eml_pano_warp_depth_work_floats(B, H, W) floats (0 when a size is refused).
+ * Limits: sizes as eml_pano_warp_f32; 1 <= steps <= 1024; 0 <= bisections <= 60.  EML_EINVAL, nothing enqueued: NULL depth
+ * or work; both outputs NULL; out_pano without pano; bad sizes; non-finite by-value parameters; steps or bisections out of
+ * range.  B == 0 returns 0. */
+size_t eml_pano_warp_depth_work_floats(int B, int H, int W);
+int eml_pano_warp_depth_f32(const float* pano, const float* depth, int B, int H, int W, int h, int w, double theta_deg,
+                            double phi_deg, double move, const double* params_dev, int steps, int bisections, float* out_pano,
+                            float* out_depth, double* hit, float* work, eml_stream_t stream);
+
+/* RegressionNetwork/data.py:75 reads a per-anchor `depth` from the training pickles and gmloss/utils.py:63-73 scales the unit
+ * anchors by it; nothing in the reference makes it.  Here: the steradian-weighted mean of a depth panorama over each anchor's
+ * Voronoi cell, with the CSR tables that eml_gt_parametrise_f64 takes (csr_ptr (N+1), csr_pix (H W)) and its pixel weight:
+ *   out[b,a] = sum_p w_p D[b,p] / sum_p w_p,   w_p = sin((row_p + 0.5) / H * pi),   p over the cell of anchor a
+ * depth (B,H,W) f32 -> out (B,N) f64.  A pixel that is not finite has weight 0; a cell whose weights sum to 0 gives NaN.  f64,
+ * one block per (anchor, image), fixed-order tree reduction: run-to-run exact.  0 <= B <= 65535 (B == 0 returns 0); EML_EINVAL
+ * for a NULL pointer or a size < 1, nothing enqueued. */
+int eml_gt_anchor_depth_f64(const float* depth, const int* csr_ptr, const int* csr_pix, int B, int H, int W, int N, double* out,
+                            eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
