@@ -43,7 +43,10 @@ def grad_slot(param=None, ptr=None):
     """Where a kernel that PRODUCES the gradient of a parameter may write it: a fresh view of the parameter's place in its
     gradient bucket (returned by a backward, autograd adopts it as ``.grad`` without a copy and the bucket needs no packing for
     it), or None -- no reducer, graph-building backward, or the place was already handed out in this backward (a module used
-    twice: autograd has to sum two tensors).  The producer must write every element."""
+    twice: autograd has to sum two tensors), or the parameter still HAS a ``.grad`` (kept over the step and zeroed in place, or
+    never cleared: that ``.grad`` is the bucket view itself, so a producer overwriting the place would be added to itself --
+    the producer then writes a tensor of its own and autograd accumulates it into the kept ``.grad``, as torch does).  The
+    producer must write every element."""
     import torch
     hit = _SLOTS.get(id(param)) if param is not None else None
     if hit is None and ptr is not None:
@@ -56,10 +59,10 @@ def grad_slot(param=None, ptr=None):
     b = red.buckets[bi]
     if param is None and b["params"][pi].data_ptr() != ptr:
         return None
-    if b["flat"] is None or pi in b["taken"]:
+    q = b["params"][pi]
+    if b["flat"] is None or pi in b["taken"] or q.grad is not None:
         return None
     b["taken"].add(pi)
-    q = b["params"][pi]
     o = b["offs"][pi]
     return b["flat"][o:o + q.numel()].view(q.shape)
 
@@ -80,7 +83,11 @@ class GradientBuckets:
     strictly in index order on every rank.  ``finish()`` -- before the optimizer step -- launches what is left (a parameter
     without a gradient in this backward counts as zero: every rank runs the same graph) and makes the current stream wait for
     the collectives.  Like DDP, construction broadcasts rank 0's parameters (and buffers, once).  One backward per optimizer
-    step with ``zero_grad(set_to_none=True)`` in between, as the trainers do: there is no ``no_sync`` accumulation mode."""
+    step, ``finish()`` after it: there is no ``no_sync`` accumulation mode, and a second backward before ``finish()`` is refused
+    with a RuntimeError (its gradients would arrive in buckets whose all-reduce is already in flight).  The trainers clear with
+    ``zero_grad(set_to_none=True)``; a ``.grad`` that is kept instead (zeroed in place, or not cleared at all) is accumulated
+    into, as torch does -- it is the bucket view, so nothing is packed for it, and ``grad_slot`` hands its place to no
+    producer."""
 
     def __init__(self, params, world, cap_mb=64, name="", buffers=()):
         import torch
@@ -131,6 +138,11 @@ class GradientBuckets:
 
     def _on_grad(self, p):
         b = self.buckets[self.where[id(p)]]
+        if b["pending"] <= 0 or any(b is x for x in self.launched):
+            # (its all-reduce may still be in flight: nothing is launched for it again, finish() cleans up as usual)
+            raise RuntimeError("GradientBuckets%s: a second backward before finish() -- a parameter's gradient arrived after "
+                               "its bucket was complete; call finish() after every backward (there is no accumulation mode "
+                               "across backwards)" % (" '%s'" % self.name if self.name else ""))
         b["pending"] -= 1
         while self.next < len(self.buckets) and self.buckets[self.next]["pending"] <= 0:
             self._launch(self.buckets[self.next])

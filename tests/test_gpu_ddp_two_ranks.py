@@ -393,3 +393,80 @@ def test_one_rank_rccl_dry_run_of_the_data_parallel_path(tmp_path):
     assert np.isfinite(dry).all()
     # DDP hands the optimizer gradients from its buckets: the same numbers (a one-rank mean), summed in the same kernels
     np.testing.assert_allclose(dry[:-1], plain[:-1], rtol=1e-6, atol=1e-7)   # measured: identical bits, 4 + 4 fresh processes
+
+
+def _elementwise_worker(rank, world, port, out_dir):
+    import copy
+    import sys
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), LOCAL_RANK="0",
+                      WORLD_SIZE=str(world), EML_DIST_BACKEND="gloo")
+    import torch.distributed as dist
+    from emlight_amd.RegressionNetwork.data import synthetic_batch
+    from emlight_amd.RegressionNetwork.engine import RegressionTrainer, init_distributed, regression_loss
+    r, local, w = init_distributed()
+    torch.manual_seed(0)
+    tr = RegressionTrainer(anchors=32, crop_hw=(64, 96), blur=.05, device="cuda:0", world=w)
+    private = copy.deepcopy(tr.model)        # after the broadcast of rank 0's parameters; no reducer, no hooks
+    batch = synthetic_batch(2, 32, (64, 96), seed=1234 + rank, device="cuda:0")
+    names = [n for n, _ in tr.model.named_parameters()]
+    sizes = [q.numel() for q in tr.model.parameters()]
+
+    def flat_grads(model):
+        return torch.cat([q.grad.detach().reshape(-1) for q in model.parameters()])
+    # this rank's own gradient of the step's loss (the criterion is the trainer's: its eps-schedule is the global batch's on both)
+    loss, _ = regression_loss(private(batch["crop"]), batch, tr.sam_loss, tr.ln)
+    loss.backward()
+    untouched = tr.buckets is None or (not tr.buckets.launched and all(b["pending"] == len(b["params"]) and not b["taken"]
+                                                                       for b in tr.buckets.buckets))
+    own = flat_grads(private)
+    gathered = [torch.empty_like(own) for _ in range(w)]
+    dist.all_gather(gathered, own)
+    # the trainer's backward: the HIP producers write into the buckets, finish() averages them over the ranks
+    net = tr.ddp if tr.ddp is not None else tr.model
+    loss, _ = regression_loss(net(batch["crop"]), batch, tr.sam_loss, tr.ln)
+    tr.optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    tr.reduce_gradients()
+    got = flat_grads(tr.model).double()
+    g0, g1 = gathered[0].double(), gathered[1].double()
+    bound = 2.0 ** -24 * (g0.abs() + g1.abs()) / 2
+    err = (got - (g0 + g1) / 2).abs()
+    ratio = torch.where(err <= bound, err / bound.clamp(min=1e-300), torch.full_like(err, float("inf")))
+    ratio = torch.where(err == 0, torch.zeros_like(err), ratio)
+    worst = int(ratio.argmax())
+    k = int(np.searchsorted(np.cumsum(sizes), worst, side="right"))
+    np.save(os.path.join(out_dir, "e%d.npy" % rank),
+            np.array([float(ratio.max()), float((err > bound).sum()), float(k), float(untouched), float(torch.isfinite(got).all()),
+                      float((gathered[0] != gathered[1]).sum()), float(got.abs().max())]))
+    if rank == 0:
+        print("two ranks elementwise: worst |grad - mean64| / bound = %.4f in %s; %d of %d elements differ between the ranks' own "
+              "gradients" % (float(ratio.max()), names[k], int((gathered[0] != gathered[1]).sum()), own.numel()), flush=True)
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_two_ranks_hip_engine_bucket_gradients_elementwise(tmp_path):
+    """What the reducer hands the optimizer, element by element: each rank runs ``RegressionTrainer(world=2)`` on its own shard
+    (B = 2, 64 x 96, the HIP encoder writing all 306 of its gradients straight into the bucket) and, on a private copy without a
+    reducer, the gradient of the same loss; the private gradients are all-gathered, and after ``backward()`` and
+    ``reduce_gradients()`` every element of every ``.grad`` satisfies ``|grad - mean64| <= 2^-24 (|g0| + |g1|) / 2``, mean64 the
+    float64 mean of the two private gradients: the gloo path halves exactly and adds once in float32 -- one rounding.  (Identical
+    replicas and finite losses, which the tests above assert, hold for a wrong gradient as well as for a right one, and Adam's
+    update does not see a scaled one.)  The private backward leaves the reducer untouched, and the shards' gradients differ.
+    Measured on the MI355X: worst ratio to the bound 1.0000 on both ranks (in fc.weight; among 1 916 743 elements some sums land
+    next to a rounding tie, so the one rounding the bound allows is used in full), no element beyond it; every element of the two
+    shards' own gradients differs."""
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    mp.spawn(_elementwise_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    e0, e1 = np.load(tmp_path / "e0.npy"), np.load(tmp_path / "e1.npy")
+    print("worst ratio to the bound: rank 0 %.4f, rank 1 %.4f" % (e0[0], e1[0]))
+    for e in (e0, e1):
+        assert e[3] == 1.0, "the private copy's backward reached the trainer's reducer"
+        assert e[4] == 1.0 and e[6] > 0.0
+        assert e[5] > 0, "the two shards gave the same gradient: the mean would prove nothing"
+        assert e[1] == 0 and e[0] <= 1.0, "%d elements beyond one float32 rounding of the mean; worst ratio %g (parameter %d)" % (e[1], e[0], e[2])
+    np.testing.assert_array_equal(e0[:3], e1[:3])      # both ranks hold the same reduced gradient
