@@ -62,16 +62,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
   // row tiles 0, 1 in registers (24), tiles 2..6 in LDS (15 KB, one ds_read_b128 per fragment and 16-channel group): all 84
   // registers + the three window rows + the accumulators do not fit the 256 registers of two waves per SIMD (measured with
   // 2 / 3 / 4 / 5 register-resident tiles: 0.618 / 0.626 / 0.627 / 0.648 ms per layer, profiles/r06_c3tp_variants.txt)
-#ifndef TP_KTR
-#define TP_KTR 2
-#endif
-  constexpr int kTR = TP_KTR;
-  float4 wf[kTR > 0 ? kTR : 1][3];
+  constexpr int kTR = 2;
+  float4 wf[kTR][3];
 #pragma unroll
   for (int tile = 0; tile < kTR; ++tile)
 #pragma unroll
     for (int J = 0; J < 3; ++J) wf[tile][J] = reinterpret_cast<const float4*>(W2t)[(tile * 3 + J) * 64 + lane];
-  __shared__ __attribute__((aligned(16))) float4 wl[(7 - kTR > 0 ? 7 - kTR : 1) * 3 * 64];
+  __shared__ __attribute__((aligned(16))) float4 wl[(7 - kTR) * 3 * 64];
   for (int e = tid; e < (7 - kTR) * 3 * 64; e += blockDim.x) wl[e] = reinterpret_cast<const float4*>(W2t)[kTR * 3 * 64 + e];
   // BN2's scale / shift: 4 distinct float4 per 16-channel group and wave -> LDS (24 registers less; 6 broadcast reads per tile)
   __shared__ __attribute__((aligned(16))) float bn_l[96];
@@ -104,11 +101,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
       for (int o = 0; o < 3; ++o) wa[ti][o] = wb[ti][o] = wc[ti][o] = 0.f;
 
     // z of (row, tile), requested one tile ahead (rows clamped into the image: unconditional loads)
-    float4 zn[3] = {make_float4(1.f, 2.f, 3.f, 4.f), make_float4(1.f, 2.f, 3.f, 4.f), make_float4(1.f, 2.f, 3.f, 4.f)};   // (TP_NOLOAD's operand)
+    float4 zn[3];
     auto zload = [&](int row, int ti) {
-#ifdef TP_NOLOAD   // experiment build: no z traffic (wrong results)
-      return;
-#endif
       const float* q = zb + ((size_t)min(row, H - 1) * W + 16 * ti) * 48;
 #pragma unroll
       for (int J = 0; J < 3; ++J) zn[J] = *reinterpret_cast<const float4*>(q + 16 * J);
@@ -134,11 +128,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
           // output row yi - dy, input pixel q output pixel q - dx
           auto scatter = [&](int ti, auto s0_tag, auto s1_tag) {
             constexpr int S0 = decltype(s0_tag)::value, S1 = decltype(s1_tag)::value;
-#ifdef TP_NOSCATTER   // experiment build: the accumulators are summed without shifts (wrong results)
-#pragma unroll
-            for (int s = S0; s < S1; ++s) wb[ti][s % 3] += d[s / 4][s % 4];
-            return;
-#endif
 #pragma unroll
             for (int s = S0; s < S1; ++s) {
               const int tap = s / 3, o = s % 3, dy = tap / 3 - 1, dx = tap % 3 - 1;
@@ -215,7 +204,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
         if (mode == kFull) row(std::integral_constant<int, kFull>{});
         else if (mode == kTop) row(std::integral_constant<int, kTop>{});
         else row(std::integral_constant<int, kBot>{});
-#ifndef TP_NOEDGE   // experiment build: no barrier, no exchange (wrong at the waves' seams): what they cost
         if (NW > 1) {
           eml::lds_barrier();
           // the left neighbour's right-edge pixel feeds this wave's pixel 0, the right neighbour's left edge pixel 15 of
@@ -240,7 +228,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
             wa[TX - 1][o] += pick(er + 4 * (6 + o), rv);
           }
         }
-#endif
       }
       // output row yi - 1 is complete
       const int yo = yi - 1;
@@ -270,10 +257,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_tp_kernel(
 #pragma unroll
             for (int o = 0; o < 3; ++o) wa[ti][o] = (keep >> (3 * ti + o)) & 1 ? wa[ti][o] * dk.scale : 0.f;
           }
-#ifndef TP_NOSTORE   // experiment build: nothing written
           struct __attribute__((packed, aligned(4))) f3 { float a, b, c; };   // one global_store_dwordx3 (4-byte aligned)
           *reinterpret_cast<f3*>(dst) = f3{wa[ti][0], wa[ti][1], wa[ti][2]};
-#endif
 #pragma unroll
           for (int o = 0; o < 3; ++o) {
             const float v = wa[ti][o];

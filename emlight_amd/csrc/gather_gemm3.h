@@ -197,10 +197,10 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e) cv[mi][e] = *reinterpret_cast<const float4*>(Fp + co[mi][e] + 4 * h);
   };
-  auto combine1 = [&](float4 (&af)[MI], const float4 (&cv)[MI][4], int mi) {   // one pixel tile (experiment builds place the two apart)
+  // one pixel tile, on register pairs (v_pk_mul_f32 / v_pk_fma_f32): half the VALU instructions of scalar fmaf chains, same
+  // sums in the same order (pairs + the two tiles behind different MFMA groups measured +2 %)
+  auto combine1 = [&](float4 (&af)[MI], const float4 (&cv)[MI][4], int mi) {
     const float4 w = wv[mi];
-#ifndef GG3_SCALARCOMBINE   // on register pairs (v_pk_mul_f32 / v_pk_fma_f32): half the VALU instructions, same sums in the same order
-                           // (experiment build GG3_SCALARCOMBINE: scalar fmaf chains; pairs + spread placement measured +2 %)
     typedef float v2f __attribute__((ext_vector_type(2)));
     v2f lo = v2f{cv[mi][0].x, cv[mi][0].y} * v2f{w.x, w.x}, hi = v2f{cv[mi][0].z, cv[mi][0].w} * v2f{w.x, w.x};
     lo += v2f{cv[mi][1].x, cv[mi][1].y} * v2f{w.y, w.y};
@@ -210,14 +210,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
     lo += v2f{cv[mi][3].x, cv[mi][3].y} * v2f{w.w, w.w};
     hi += v2f{cv[mi][3].z, cv[mi][3].w} * v2f{w.w, w.w};
     af[mi] = make_float4(lo.x, lo.y, hi.x, hi.y);
-#else
-    af[mi].x = fmaf(cv[mi][3].x, w.w, fmaf(cv[mi][2].x, w.z, fmaf(cv[mi][1].x, w.y, cv[mi][0].x * w.x)));
-    af[mi].y = fmaf(cv[mi][3].y, w.w, fmaf(cv[mi][2].y, w.z, fmaf(cv[mi][1].y, w.y, cv[mi][0].y * w.x)));
-    af[mi].z = fmaf(cv[mi][3].z, w.w, fmaf(cv[mi][2].z, w.z, fmaf(cv[mi][1].z, w.y, cv[mi][0].z * w.x)));
-    af[mi].w = fmaf(cv[mi][3].w, w.w, fmaf(cv[mi][2].w, w.z, fmaf(cv[mi][1].w, w.y, cv[mi][0].w * w.x)));
-#endif
   };
-  auto combine = [&](float4 (&af)[MI], const float4 (&cv)[MI][4]) {   // grid_sample's order: nw, ne, sw, se (= gg2's commit)
+  // both tiles as scalar fmaf chains in grid_sample's order: nw, ne, sw, se (= gg2's commit); the chunk's first fragments
+  auto combine = [&](float4 (&af)[MI], const float4 (&cv)[MI][4]) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       const float4 w = wv[mi];
@@ -245,11 +240,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
   float4 af0[MI], af1[MI];
   for (int ch = c_begin; ch < c_end; ++ch) {
     // every wave has passed the barrier that closed the previous chunk's last tap: nobody reads Fp any more
-#ifndef GG3_NOFP
     store_fp();
     eml::lds_barrier();
     load_fp(min(ch + 1, c_end - 1));                   // the next chunk's footprint, a whole chunk (9+ taps) ahead
-#endif
     {
       float4 cv[MI][4];
       load_table(g & 1);
@@ -265,9 +258,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
       if (n_ch == c_end) { n_vt = nvt - 1; n_ch = ch; }
       const int n_tap = ngrp == 2 ? (n_vt >> 1) : n_vt;
       __builtin_amdgcn_sched_barrier(0);
-#ifndef GG3_NOTAB   // (experiment builds, tools/exp/gg3_variants.sh: pieces of the loop removed one at a time -- wrong results)
       table_dma(n_vt, buf ^ 1);                        // first: the counted wait below (vmcnt(NBD)) then covers it
-#endif
       const float* bb = Bs + (size_t)buf * BN * kLdB + (128 * wn + r) * kLdB;
       const int sw = bswz(r);
       float4 cv[MI][4];
@@ -275,19 +266,17 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
       // alternate so that a dependent MFMA is two issues = 64 cycles behind its producer).  Everything else of the (chunk, tap)
       // is pinned behind a named group -- each piece early enough for its consumer, none bunched in front of the MFMAs:
       //   half 0: the corner reads of this tap's second K-half in front; one dense-operand DMA behind groups 0..3;
-      //           combine (second half's fragments) behind group 5
+      //           combine (second half's fragments) behind groups 4 and 6, one pixel tile each
       //   half 1: behind group 1 the counted wait for the next tap's table (issued a K-half ago; the NBD dense-operand DMAs
       //           behind it may still fly) and its entries -- wave-private, no barrier needed; behind group 2 the offsets;
-      //           behind group 3 the next tap's first-half corners (the footprint is static within a chunk); combine behind 6
+      //           behind group 3 the next tap's first-half corners (the footprint is static within a chunk); combine behind 5 and 7
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         float4 bf[NI];
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
           bf[ni] = *reinterpret_cast<const float4*>(bb + 16 * ni * kLdB + 4 * ((2 * kk + h) ^ sw));
-#ifndef GG3_NOCORNER
         if (h == 0) read_corners(cv, 1);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
@@ -297,42 +286,24 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gather_gemm3_kernel(
             for (int mi = 0; mi < MI; ++mi)
               acc[ni][mi] = mfma16(f4c(bf[ni], t), f4c(h == 0 ? af0[mi] : af1[mi], t), acc[ni][mi]);
           if (h == 0) {
-#ifndef GG3_NOBDMA
             if (ni < NBD) b_dma(ni, n_tap, n_ch * kBK, buf ^ 1);
-#endif
-#ifndef GG3_NOCORNER
-#ifndef GG3_BUNCHED   // the two pixel tiles' combines behind different MFMA groups (experiment build GG3_BUNCHED: both behind one)
-            if (ni == 4) combine1(af1, cv, 0);
+            if (ni == 4) combine1(af1, cv, 0);           // the two pixel tiles' combines behind different MFMA groups
             if (ni == 6) combine1(af1, cv, 1);
-#else
-            if (ni == 5) combine(af1, cv);
-#endif
-#endif
           } else {
-#ifndef GG3_NOTAB
             if (ni == 1) {
               asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBD) : "memory");
               load_table(buf ^ 1);
             }
             if (ni == 2) table_offsets();
-#endif
-#ifndef GG3_NOCORNER
             if (ni == 3) read_corners(cv, 0);
-#ifndef GG3_BUNCHED
             if (ni == 5) combine1(af0, cv, 0);
             if (ni == 7) combine1(af0, cv, 1);
-#else
-            if (ni == 6) combine(af0, cv);
-#endif
-#endif
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef GG3_NOBAR
       eml::lds_barrier();
-#endif
     }
   }
 

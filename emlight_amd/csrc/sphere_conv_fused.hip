@@ -25,7 +25,6 @@
 #include "eml_common.h"
 #include "gather_gemm2.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -64,6 +63,8 @@ __device__ __forceinline__ float4 combine(const float4 (&v)[4], const float4& w)
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// The round-2 kernel.  Bilinear tables of layers with C >= 64 go to gather_gemm2.h (launch_gather_gemm below); this one is the
+// kernel for the rest: single-entry tables (ke == 1), C < 64 (one chunk per tap), and tables whose 32-bit offsets do not fit.
 // The same kernel serves the INPUT gradient: dx[q][c] = sum_{tap,o} Dg[q][tap][o] * W2t[c][tap*O + o] with
 // Dg[q][tap][o] = sum_e w_e dY[p_e][o] gathered through the TRANSPOSED tap table (entries of input pixel q grouped by
 // tap: almost always 4, up to 8 in the few rows next to the poles).  `ke` = table entries per (pixel, tap): 4, or 8 with
@@ -296,11 +297,11 @@ __global__ __launch_bounds__(256, 2) void sphere_conv_fwd_fused_kernel(
 // ------------------------------------------------------------------------------------------------ weight gradient
 // grid = (column tiles of the (tap, c) axis, row tiles of O, split-K); partial[z][O][9C].  BMO = output channels per
 // tile: 128, or 64 for the 64-channel layers (a 128-row tile would spend half of its MFMAs on padding).
-// VR (round 4): MFMA row / column r of tile j stands for channel MI*r + j (resp. NI*r + j) of the wave's span instead of
+// MFMA row / column r of tile j stands for channel MI*r + j (resp. NI*r + j) of the wave's span instead of
 // 16*j + r -- which channel a row index means is free as long as the epilogue agrees -- so a lane's MI (NI) operand values of a
 // k-step are CONSECUTIVE floats of one LDS row: one ds_read_b128 (b64) instead of four (two) ds_read_b32, 16 LDS read
-// instructions per chunk and wave instead of 64, and the result leaves as 16-byte stores.  Layout and commits are unchanged.
-template <int BN, int BMO, bool VR>
+// instructions per chunk and wave instead of 64, and the result leaves as 16-byte stores.
+template <int BN, int BMO>
 __global__ __launch_bounds__(256, 2) void sphere_conv_wgrad_fused_kernel(
     const float* __restrict__ X, const int* __restrict__ idx, const float* __restrict__ wgt,
     const float* __restrict__ dY /*[M][O]*/, float* __restrict__ partial, int M, int HW, int Po, int C, int O,
@@ -310,6 +311,8 @@ __global__ __launch_bounds__(256, 2) void sphere_conv_wgrad_fused_kernel(
   float* Gs = smem + 2 * kBK * kLdW;      // [2][kBK][kLdW]  Ag tile   [pixel][c]
   constexpr int NI = BN / 32;
   constexpr int MI = BMO / 32;            // 16-row tiles per wave along O
+  typedef float vmi __attribute__((ext_vector_type(MI)));   // a lane's operand values of one k-step: one LDS read each
+  typedef float vni __attribute__((ext_vector_type(NI)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, kk = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
@@ -422,26 +425,12 @@ __global__ __launch_bounds__(256, 2) void sphere_conv_wgrad_fused_kernel(
     const size_t xn = x1;
     begin_chunk(nxt, tn);
     __builtin_amdgcn_sched_barrier(0);
-    const float* db = Ds + (size_t)buf * kBK * kLdW + (BMO / 2) * wm + (VR ? MI * r : r);
-    const float* gb = Gs + (size_t)buf * kBK * kLdW + (BN / 2) * wn + (VR ? NI * r : r);
+    const float* db = Ds + (size_t)buf * kBK * kLdW + (BMO / 2) * wm + MI * r;
+    const float* gb = Gs + (size_t)buf * kBK * kLdW + (BN / 2) * wn + NI * r;
 #pragma unroll
     for (int ks = 0; ks < kSteps; ++ks) {
-      float a[MI], b[NI];
-      if constexpr (VR) {
-        typedef float vmi __attribute__((ext_vector_type(MI)));
-        typedef float vni __attribute__((ext_vector_type(NI)));
-        const vmi av = *reinterpret_cast<const vmi*>(db + (4 * ks + kk) * kLdW);
-        const vni bv = *reinterpret_cast<const vni*>(gb + (4 * ks + kk) * kLdW);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) a[mi] = av[mi];
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) b[ni] = bv[ni];
-      } else {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) a[mi] = db[(4 * ks + kk) * kLdW + 16 * mi];
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) b[ni] = gb[(4 * ks + kk) * kLdW + 16 * ni];
-      }
+      const vmi a = *reinterpret_cast<const vmi*>(db + (4 * ks + kk) * kLdW);
+      const vni b = *reinterpret_cast<const vni*>(gb + (4 * ks + kk) * kLdW);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -465,34 +454,19 @@ __global__ __launch_bounds__(256, 2) void sphere_conv_wgrad_fused_kernel(
     }
     eml::lds_barrier();
   }
-  // partial[z][o][tap*C + c]: lane (r, kk) holds rows o = 4kk + g, column c = r of each 16x16 tile
+  // partial[z][o][tap*C + c]: lane (r, kk) holds rows i = 4kk + g, column r of each 16x16 tile; in tile (mi, ni) row i is
+  // output channel MI*i + mi and column r is input channel NI*r + ni
   float* out = partial + (size_t)bz * O * 9 * C;
-  if constexpr (VR) {
-    // tile (mi, ni): row index i = 4kk + g is output channel MI*i + mi, column index r is input channel NI*r + ni
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int o = o0 + (BMO / 2) * wm + MI * (4 * kk + g) + mi;
-        if (o < O) {
-          typedef float vni __attribute__((ext_vector_type(NI)));
-          vni v;
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) v[ni] = acc[mi][ni][g];
-          *reinterpret_cast<vni*>(out + (size_t)o * 9 * C + tap * C + c0 + (BN / 2) * wn + NI * r) = v;
-        }
-      }
-    return;
-  }
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int o = o0 + (BMO / 2) * wm + 16 * mi + 4 * kk + g;
+      const int o = o0 + (BMO / 2) * wm + MI * (4 * kk + g) + mi;
       if (o < O) {
+        vni v;
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          out[(size_t)o * 9 * C + tap * C + c0 + (BN / 2) * wn + 16 * ni + r] = acc[mi][ni][g];
+        for (int ni = 0; ni < NI; ++ni) v[ni] = acc[mi][ni][g];
+        *reinterpret_cast<vni*>(out + (size_t)o * 9 * C + tap * C + c0 + (BN / 2) * wn + NI * r) = v;
       }
     }
 }
@@ -509,21 +483,11 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
 }  // namespace
 
 namespace {
-// EML_GG_V1=1: A/B switch back to the round-2 kernel for every table (read once)
-bool gg_v1_enabled() {
-  static const bool on = [] { const char* v = getenv("EML_GG_V1"); return v && v[0] == '1'; }();
-  return on;
-}
 // gather_gemm2's per-pixel 32-bit BYTE offsets are relative to the tile's first sample: a 128-pixel tile spans at most
 // (127 / Po + 2) samples of HW * C floats each (the HW * C bound alone does not cover Po < 128)
 bool gg2_offsets_fit(long HW, int C, int Po) {
   return (unsigned long long)HW * C < (1ull << 29) &&
          (unsigned long long)((gg2::kBM - 1) / Po + 2) * (unsigned long long)HW * C * 4ull < (1ull << 32);
-}
-// EML_GG_NOSHARE=1: A/B switch -- ignore EML_TAP_ROWSHARE (the 16-load gather for every table)
-bool gg_noshare() {
-  static const bool on = [] { const char* v = getenv("EML_GG_NOSHARE"); return v && v[0] == '1'; }();
-  return on;
 }
 int launch_gather_gemm(const char* what, const float* X, const int* idx, const float* wgt, const float* W2, const float* bias,
                        float* Y, int B, int HW, int Po, int C, int O, int ke, const unsigned char* rowmax,
@@ -537,18 +501,18 @@ int launch_gather_gemm(const char* what, const float* X, const int* idx, const f
   // the same box (profiles/r04_gg2_variants.jsonl, variant v2.2).  It needs two chunks per tap (C >= 64) and its 32-bit
   // offsets to reach two samples / the weight tile; single-entry (planar) tables keep the round-2 kernel, which schedules
   // their four loads per chunk better (vgg 64 -> 64: 107 against 98 TF/s).
-  if (ke != 1 && C >= 64 && gg2_offsets_fit(HW, C, Po) && (unsigned long long)O * 9 * C < (1ull << 30) && !gg_v1_enabled()) {
+  if (ke != 1 && C >= 64 && gg2_offsets_fit(HW, C, Po) && (unsigned long long)O * 9 * C < (1ull << 30)) {
     const long n_mt2 = (M + gg2::kBM - 1) / gg2::kBM, per_xcd2 = (n_mt2 + 7) / 8;
     const dim3 grid2((unsigned)(8 * per_xcd2 * (O / bn)));
 #define EML_LAUNCH_GG2(BNV, LPPV, SHV)                                                                               \
   do {                                                                                                              \
-    auto kern = gg2::gather_gemm2_kernel<BNV, 256, LPPV, false, false, false, SHV>;                                 \
-    EML_ENSURE_LDS(kern, (gg2::lds_bytes<BNV, 256>()));                                                             \
-    hipLaunchKernelGGL(kern, grid2, dim3(256), (gg2::lds_bytes<BNV, 256>()), (hipStream_t)stream, X, idx, wgt, W2,  \
+    auto kern = gg2::gather_gemm2_kernel<BNV, LPPV, false, SHV>;                                                    \
+    EML_ENSURE_LDS(kern, gg2::lds_bytes<BNV>());                                                                    \
+    hipLaunchKernelGGL(kern, grid2, dim3(gg2::kNT), gg2::lds_bytes<BNV>(), (hipStream_t)stream, X, idx, wgt, W2,    \
                        bias, Y, (int)M, HW, Po, C, O, ke, rowmax, res, slope, gg2::SpadeEpilogue{});                \
   } while (0)
     // round 5: row-shared corners (10 gathered loads per chunk instead of 16) where the caller vouches for the table
-    const bool share = (table_flags & EML_TAP_ROWSHARE) && ke == 4 && Po % 4 == 0 && !gg_noshare();
+    const bool share = (table_flags & EML_TAP_ROWSHARE) && ke == 4 && Po % 4 == 0;
     if (share) {
       if (bn == 128) EML_LAUNCH_GG2(128, 8, true); else EML_LAUNCH_GG2(64, 8, true);
     } else {
@@ -557,6 +521,7 @@ int launch_gather_gemm(const char* what, const float* X, const int* idx, const f
 #undef EML_LAUNCH_GG2
     return eml::check_launch(what);
   }
+  // everything else -- ke == 1, C < 64, offsets that do not fit -- is the round-2 kernel's
   const size_t lds = (size_t)(2 * kBM * kLdF + 2 * bn * kLdF) * sizeof(float);
   const long n_mt = (M + kBM - 1) / kBM, per_xcd = (n_mt + 7) / 8;
   const dim3 grid((unsigned)(8 * per_xcd * (O / bn)));   // 1-D: the kernel maps id -> (XCD band, pixel tile, O-tile)
@@ -630,15 +595,15 @@ extern "C" int eml_sphere_conv_spade_fwd_f32(const float* actv, const int* idx, 
   const dim3 grid((unsigned)(8 * per_xcd * (O / 128)));
   if (table_flags & ~EML_TAP_ROWSHARE) return eml::fail(EML_EINVAL, "eml_sphere_conv_spade_fwd_f32: unknown table_flags %d", table_flags);
   const gg2::SpadeEpilogue mod{x, mean, istd, gamma_out, up2 ? 1 : 0, H, W};
-  if ((table_flags & EML_TAP_ROWSHARE) && HW % 4 == 0 && !gg_noshare()) {
-    auto kern = gg2::gather_gemm2_kernel<128, 256, 8, false, false, true, true>;
-    EML_ENSURE_LDS(kern, (gg2::lds_bytes<128, 256>()));
-    hipLaunchKernelGGL(kern, grid, dim3(256), (gg2::lds_bytes<128, 256>()), (hipStream_t)stream, actv, idx, wgt, W2r, bias_r, Y,
+  if ((table_flags & EML_TAP_ROWSHARE) && HW % 4 == 0) {
+    auto kern = gg2::gather_gemm2_kernel<128, 8, true, true>;
+    EML_ENSURE_LDS(kern, gg2::lds_bytes<128>());
+    hipLaunchKernelGGL(kern, grid, dim3(gg2::kNT), gg2::lds_bytes<128>(), (hipStream_t)stream, actv, idx, wgt, W2r, bias_r, Y,
                        (int)M, HW, HW, Cin, O, 4, nullptr, nullptr, act_slope, mod);
   } else {
-    auto kern = gg2::gather_gemm2_kernel<128, 256, 4, false, false, true>;
-    EML_ENSURE_LDS(kern, (gg2::lds_bytes<128, 256>()));
-    hipLaunchKernelGGL(kern, grid, dim3(256), (gg2::lds_bytes<128, 256>()), (hipStream_t)stream, actv, idx, wgt, W2r, bias_r, Y,
+    auto kern = gg2::gather_gemm2_kernel<128, 4, true>;
+    EML_ENSURE_LDS(kern, gg2::lds_bytes<128>());
+    hipLaunchKernelGGL(kern, grid, dim3(gg2::kNT), gg2::lds_bytes<128>(), (hipStream_t)stream, actv, idx, wgt, W2r, bias_r, Y,
                        (int)M, HW, HW, Cin, O, 4, nullptr, nullptr, act_slope, mod);
   }
   return eml::check_launch("eml_sphere_conv_spade_fwd_f32");
@@ -677,23 +642,15 @@ extern "C" int eml_sphere_conv_wgrad_fused_f32(const float* X, const int* idx, c
   // The tiles of a K-split on one XCD (see the kernel) where a split has at most 18 of them -- then the 7 splits an XCD
   // holds at a time are all resident: +1.6 ... 2.6 % on the 128 x 256 layers, +-0 at 64 x 128; with 36 / 72 tiles per split
   // (128 -> 512, 512 -> 256) the same order LOSES 12 / 22 % (profiles/r06_wgrad_xcd.txt).  Needs a multiple of 8 splits: the
-  // remainder of the caller's split_k is not used (partial rows past it are never summed).  EML_WG_XCD=0: natural order (A/B).
-  static const bool xcd_env = [] { const char* v = getenv("EML_WG_XCD"); return !(v && v[0] == '0'); }();
-  const int xg = (xcd_env && split_k >= 8 && 9 * (C / bn) * ((O + bmo - 1) / bmo) <= 18) ? 1 : 0;
+  // remainder of the caller's split_k is not used (partial rows past it are never summed).
+  const int xg = (split_k >= 8 && 9 * (C / bn) * ((O + bmo - 1) / bmo) <= 18) ? 1 : 0;
   if (xg) split_k &= ~7;
   const dim3 grid(9 * (C / bn), (O + bmo - 1) / bmo, split_k);
-  static const bool scalar_reads = [] { const char* v = getenv("EML_WG_V1"); return v && v[0] == '1'; }();   // A/B switch
 #define EML_LAUNCH_WGRAD(BNV, BMV)                                                                                   \
   do {                                                                                                              \
-    if (scalar_reads) {                                                                                             \
-      EML_ENSURE_LDS((&sphere_conv_wgrad_fused_kernel<BNV, BMV, false>), lds);                                      \
-      hipLaunchKernelGGL((sphere_conv_wgrad_fused_kernel<BNV, BMV, false>), grid, dim3(256), lds, (hipStream_t)stream, X, idx, \
-                         wgt, dY, partial, (int)M, HW, Po, C, O, xg);                                                \
-    } else {                                                                                                        \
-      EML_ENSURE_LDS((&sphere_conv_wgrad_fused_kernel<BNV, BMV, true>), lds);                                       \
-      hipLaunchKernelGGL((sphere_conv_wgrad_fused_kernel<BNV, BMV, true>), grid, dim3(256), lds, (hipStream_t)stream, X, idx, \
-                         wgt, dY, partial, (int)M, HW, Po, C, O, xg);                                                \
-    }                                                                                                               \
+    EML_ENSURE_LDS((&sphere_conv_wgrad_fused_kernel<BNV, BMV>), lds);                                               \
+    hipLaunchKernelGGL((sphere_conv_wgrad_fused_kernel<BNV, BMV>), grid, dim3(256), lds, (hipStream_t)stream, X, idx, wgt, \
+                       dY, partial, (int)M, HW, Po, C, O, xg);                                                      \
   } while (0)
   if (bn == 128) {
     if (bmo == 128) EML_LAUNCH_WGRAD(128, 128); else EML_LAUNCH_WGRAD(128, 64);

@@ -24,6 +24,7 @@ no output of any configuration lies on the other side of zero from its float64 v
     narrow-project 2x64x3x16x32 0.002 (without a bias 0.002)   2x192x2x12x24 stride 2 0.002   2x512x3x8x16 0.003   1x64x3x2x4 0.001
     narrow-onepass 2x64x3x16x32 0.001                           narrow-shape-activation 2x64x3x16x32 slope 0.2 0.004
     fused 2x64x64x8x16 0.006 (residual + 0.2: 0.005, without a bias 0.006)   2x32x64x8x16 0.004   3x128x64x16x32 stride 2 0.008
+          2x64x128x8x16 0.009   2x64x128x16x32 stride 2 0.006   2x128x64x8x16 0.007   2x128x128x8x16 0.008   1x64x64x8x16 0.006
     library 2x16x8x8x16 0.003   2x6x12x16x32 stride 2 0.002 (residual + ReLU 0.002)
     lowres 2x128x128x8x16 residual + 0.2 0.004   5x128x128x4x8 ReLU 0.004
     planar 2x64x64x8x16 ReLU 0.004   2x3x64x16x32 ReLU 0.001
@@ -80,6 +81,12 @@ CONFIGS = (
     + [_c("fused", (2, 64, 64, 8, 16, 1), fused_min_bytes=0), _c("fused", (2, 64, 64, 8, 16, 1), residual=True, slope=0.2, fused_min_bytes=0),
        _c("fused", (2, 64, 64, 8, 16, 1), bias=False, fused_min_bytes=0),
        _c("fused", (2, 32, 64, 8, 16, 1), fused_min_bytes=0), _c("fused", (3, 128, 64, 16, 32, 2), fused_min_bytes=0)]
+    # one row per instantiation of csrc/sphere_conv_fused.hip the rows above leave out.  Forward: the gather-GEMM's 128-channel
+    # tile with row-shared corners (stride 1, O = 128) and without (stride 2).  Weight gradient, (BN, BMO) from (C, O): (64, 128),
+    # (128, 64), (128, 128) -- (64, 64) is the first row -- at 2 x 128 pixels: 8 K-splits, the tiles of a split on one XCD; and
+    # one sample alone: 4 K-splits, natural tile order
+    + [_c("fused", s, fused_min_bytes=0) for s in ((2, 64, 128, 8, 16, 1), (2, 64, 128, 16, 32, 2), (2, 128, 64, 8, 16, 1),
+                                                   (2, 128, 128, 8, 16, 1), (1, 64, 64, 8, 16, 1))]
     # im2col + library GEMMs with the operand kept, natural dispatch
     + [_c("library", (2, 16, 8, 8, 16, 1)), _c("library", (2, 6, 12, 16, 32, 2)), _c("library", (2, 6, 12, 16, 32, 2), residual=True, slope=0.0)]
     # the footprint gather-GEMM, forward and input gradient

@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from emlight_amd import _lib
 if os.environ.get("EML_LIB_PATH"):
-    _lib.LIB_PATH = os.environ["EML_LIB_PATH"]   # experiment builds (tools/exp/c3tp_variants.sh)
+    _lib.LIB_PATH = os.environ["EML_LIB_PATH"]   # another build of the library (tools/exp_build.sh)
 L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 cu = torch.cuda.get_device_properties(0).multi_processor_count

@@ -1,5 +1,5 @@
 """Weight gradient of the fused SphereConv at the projector's high-resolution shapes, B = 32: ms per call (HIP events).
-EML_WG_XCD=0/1 and EML_WGRAD_WGS are read from the environment (A/B of the tile order).
+EML_WGRAD_WGS is read from the environment.
     python tools/bench_wgrad_xcd.py"""
 import os
 import sys
