@@ -279,6 +279,10 @@ EXT_SIGNATURES = {
     "eml_pano_warp_depth_f32": (_int, [_f32p, _f32p, _int, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, _f64p, _int, _int, _f32p, _f32p, _f64p, _f32p, _stream]),
     "eml_gt_anchor_depth_f64": (_int, [_f32p, _i32p, _i32p, _int, _int, _int, _int, _f64p, _stream]),
+    # object insertion: the shadow the occluder spheres cast on a ground plane
+    "eml_ground_shadow_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int]),
+    "eml_ground_shadow_f32": (_int, [_f32p, _int, _int, _int, _f32p, _int, _f32p, _int, _int, _int, ctypes.c_double,
+                                     ctypes.c_double, _f32p, _f32p, _f32p, _f32p, _stream]),
 }
 
 _lock = threading.Lock()

@@ -8,16 +8,23 @@ estimation is for (the reference's README; its tree has no code for the step).  
 * ``shade_gbuffer`` / ``composite`` / ``insert_object``: every covered pixel of a G-buffer (camera-space normals, coverage,
   ``kd``, ``ks``, ``km``) lit by three lookups and composited over the photograph (``csrc/gbuffer_shade.hip``).
 * ``gbuffer_sphere``: the G-buffer of a sphere drawn as section 15 draws it, at a pixel position.
+* ``ground_shadow``: the shadow the object, given as a few occluder spheres, casts on a ground plane: per pixel of the
+  plane the panorama's irradiance with the spheres in the way over the irradiance without them (``csrc/ground_shadow.hip``,
+  DESIGN.md section 28; ``tests/shadow_oracle.py``).  ``sphere_occluder`` is the occluder that goes with ``gbuffer_sphere``.
 
 Forward only: a tensor that requires grad is refused (``emlight_amd.insert_grad`` is the differentiable interface).
 Everything only enqueues work.
 
     python -m emlight_amd.insert --pano pred.npy --image crop.npy --gbuffer DIR --fov 60 [--exposure A] [--out out.npy]
     python -m emlight_amd.insert --pano pred.npy --image crop.npy --sphere CX CY RADIUS [--kd 0.8 --ks 0.2 --km 0]
+    python -m emlight_amd.insert ... --ground HEIGHT [--ground_normal NX NY NZ] [--depth Z] [--occluders FILE.npy]
 
 ``DIR`` holds ``normal.npy`` (3, h, w), ``coverage.npy`` (h, w) or (1, h, w) and any of ``kd.npy``, ``ks.npy``, ``km.npy``
 (3, h, w); the image is the HDR crop (3, h, w).  Without ``--exposure`` the scale is ``TonemapHDR``'s alpha of the image,
-raised to gamma so that the object is tonemapped exactly as the photograph is.
+raised to gamma so that the object is tonemapped exactly as the photograph is.  ``--ground HEIGHT`` puts a ground plane
+``HEIGHT`` below the camera (normal ``--ground_normal``, default straight up) and multiplies the HDR image by the shadow ratio
+before it is tonemapped; the exposure is still the unshadowed image's.  The occluder is the sphere itself, ``--depth Z`` away
+along its centre's ray (``--sphere``), or the ``(K, 4)`` camera-space spheres of ``--occluders`` (``--gbuffer``).
 """
 import argparse
 import ctypes
@@ -31,6 +38,7 @@ from . import _lib
 
 DIFFUSE = "diffuse"
 MAX_LOBES = 8
+MAX_OCCLUDERS = 16
 
 
 def _forward_only(t, name):
@@ -265,6 +273,103 @@ def gbuffer_sphere(h, w, centre, radius, device="cuda", batch=1):
     return normal[None].expand(batch, 3, h, w).contiguous(), cov[None].expand(batch, 1, h, w).contiguous()
 
 
+def _filled(values, device):
+    """A 1-d float32 device tensor of a few numbers.  One tiny fill kernel per number instead of ``torch.tensor(values,
+    device=...)``: that would be a copy from pageable host memory, which synchronises the stream; fills only enqueue."""
+    t = torch.empty(len(values), dtype=torch.float32, device=device)
+    for k, v in enumerate(values):
+        t[k].fill_(float(v))
+    return t
+
+
+def _plane_arg(plane, B, device):
+    """A 4-tuple ``(nx, ny, nz, d)`` or a ``(B, 4)`` device tensor -> (tensor, stride in floats)."""
+    if isinstance(plane, torch.Tensor):
+        t = _lib.require_gpu_tensor(_forward_only(plane, "plane"), "plane")
+        if tuple(t.shape) != (B, 4):
+            raise ValueError("plane: expected (nx, ny, nz, d) or a tensor %s, got %s" % ((B, 4), tuple(t.shape)))
+        return t, 4
+    vals = [float(v) for v in plane]
+    if len(vals) != 4 or not all(math.isfinite(v) for v in vals):
+        raise ValueError("plane: expected four finite numbers (nx, ny, nz, d), got %r" % (plane,))
+    if vals[0] == 0.0 and vals[1] == 0.0 and vals[2] == 0.0:
+        raise ValueError("plane: the normal is zero, got %r" % (plane,))
+    if not vals[3] > 0.0:
+        raise ValueError("plane: d > 0 is required (the camera is on the lit side: n.q + d = 0 on the plane), got %r" % (plane,))
+    return _filled(vals, device), 0
+
+
+def ground_shadow(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, view_azimuth_deg=180.0, size=None, image=None):
+    """The shadow ``occluders (B, K, 4)`` -- spheres ``(cx, cy, cz, r)`` in camera space (x image right, y image up, z towards
+    the camera), ``0 <= K <= 16``, ``r <= 0`` or NaN ignored, ``r = inf`` holds every point -- cast on the ground plane
+    ``n.q + d = 0`` (``plane = (nx, ny, nz, d)`` in camera space, one for the batch or a ``(B, 4)`` device tensor; the four numbers are the equation's coefficients, the
+    normal is normalised here and ``d`` with it, so with a unit normal ``d`` is the camera's distance; ``d > 0``; the default
+    is a floor one unit below a level camera) under the panorama ``pano (B, 3, H, 2H)``, seen by ``shade_gbuffer``'s camera.
+    -> ``ratio (B, 3, h, w)`` in [0, 1]: per pixel that shows the plane and per channel, the cosine-weighted irradiance with
+    the spheres in the way over the irradiance without them; exactly 1 where the pixel misses the plane or the channel's
+    irradiance is 0, exactly 0 where the plane's point is inside a sphere.  ``size=(h, w)`` is required without ``image``;
+    with ``image (B, 3, h, w)`` (the HDR photograph) -> ``(ratio, shadowed)`` with ``shadowed = image * ratio``, what
+    ``composite`` takes as the background once tonemapped.  ``ratio`` does not look at the object's coverage: the composite
+    overwrites those pixels.  A plane given as a device tensor cannot be checked here: a zero normal or ``d <= 0`` makes that
+    image NaN.  ``eml_ground_shadow_f32``; only enqueues work, run-to-run exact, an image's result does not depend on the
+    batch.  The unit of length is arbitrary, shared by plane and spheres."""
+    fov, az = _camera(fov_deg, view_azimuth_deg)
+    if fov == 0.0:
+        raise ValueError("fov_deg must be in (0, 180): the rays of an orthographic camera would need origins, got %r" % (fov_deg,))
+    x = _pano_arg(pano)
+    B, _, H, W = x.shape
+    occ = _lib.require_gpu_tensor(_forward_only(occluders, "occluders"), "occluders")
+    if occ.dim() != 3 or occ.shape[0] != B or occ.shape[2] != 4 or occ.shape[1] > MAX_OCCLUDERS:
+        raise ValueError("occluders: expected (%d, K, 4) with K <= %d, got %s" % (B, MAX_OCCLUDERS, tuple(occ.shape)))
+    K = occ.shape[1]
+    img = None
+    if image is not None:
+        img = _lib.require_gpu_tensor(_forward_only(image, "image"), "image")
+        if img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
+            raise ValueError("image: expected (%d, 3, h, w), got %s" % (B, tuple(img.shape)))
+        if size is not None and tuple(int(v) for v in size) != tuple(img.shape[2:]):
+            raise ValueError("size %r does not match the image's %s" % (size, tuple(img.shape[2:])))
+        h, w = img.shape[2:]
+    elif size is None:
+        raise ValueError("size=(h, w) is required without image")
+    else:
+        h, w = (int(v) for v in size)
+    if h < 2 or w < 2:
+        raise ValueError("the image size: expected h, w >= 2, got %s" % ((h, w),))
+    pl, stride = _plane_arg(plane, B, x.device)
+    ratio = torch.empty(B, 3, h, w, dtype=torch.float32, device=x.device)
+    shadowed = torch.empty_like(ratio) if img is not None else None
+    if B > 0:
+        L = _lib.lib()
+        work = torch.empty(max(1, (L.eml_ground_shadow_work_floats(B, H, h, w, K) + 1) // 2), dtype=torch.float64,
+                           device=x.device)                          # doubles: 8-byte aligned
+        _lib.check(L.eml_ground_shadow_f32(_lib.ptr(x), B, H, W, _lib.ptr(pl), stride, _lib.ptr(occ) if K > 0 else None, K,
+                                           h, w, fov, az, _lib.ptr(img), _lib.ptr(ratio), _lib.ptr(shadowed), _lib.ptr(work),
+                                           _lib.current_stream()), "eml_ground_shadow_f32")
+    return ratio if img is None else (ratio, shadowed)
+
+
+def sphere_occluder(h, w, centre, radius, depth, fov_deg=60.0, device="cuda"):
+    """The ``(1, 1, 4)`` camera-space occluder of the sphere ``gbuffer_sphere(h, w, centre, radius)`` draws, ``depth`` away from
+    the camera: its centre lies at distance ``depth`` along the ray of pixel ``centre = (cx, cy)`` (column, row; fractions are
+    fine), its radius is ``radius * 2 tan(fov / 2) / (w - 1) * depth``, the width of ``radius`` pixels at that distance.  A
+    sphere's perspective image is only approximately that disc (it is an ellipse away from the image centre, and the disc's
+    rim is seen at the tangent cone, slightly in front of the centre): occluder and drawing agree to first order in
+    ``radius / depth``."""
+    h, w = int(h), int(w)
+    cx, cy = (float(v) for v in centre)
+    rad, dep, fov = float(radius), float(depth), float(fov_deg)
+    if (h < 2 or w < 2 or not (rad > 0.0 and dep > 0.0 and 0.0 < fov < 180.0)
+            or not all(math.isfinite(v) for v in (cx, cy, rad, dep))):
+        raise ValueError("sphere_occluder: h, w >= 2, a finite centre, radius > 0, depth > 0 and fov_deg in (0, 180), got %r"
+                         % ((h, w, centre, radius, depth, fov_deg),))
+    scl = math.tan(math.radians(fov) / 2.0)
+    sx = scl * (2.0 * cx / (w - 1) - 1.0)
+    sy = (scl * h / w) * (2.0 * cy / (h - 1) - 1.0)
+    t = dep / math.sqrt(sx * sx + sy * sy + 1.0)                      # the ray is (sx, -sy, -1) in camera space
+    return _filled((t * sx, -t * sy, -t, rad * 2.0 * scl / (w - 1) * dep), device).view(1, 1, 4)
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def _load(path, shapes, name):
     a = np.asarray(np.load(path), dtype=np.float32)
@@ -293,15 +398,28 @@ def build_parser():
     ap.add_argument("--phong", type=float, default=50.0)
     ap.add_argument("--gamma", type=float, default=2.4)
     ap.add_argument("--exposure", type=float, default=None, help="default: TonemapHDR's alpha of the image, raised to gamma")
+    ap.add_argument("--ground", type=float, default=None, metavar="HEIGHT",
+                    help="cast the object's shadow on a ground plane HEIGHT below the camera (in the units of --depth / --occluders)")
+    ap.add_argument("--ground_normal", nargs=3, type=float, default=(0.0, 1.0, 0.0), metavar=("NX", "NY", "NZ"),
+                    help="the plane's normal in camera space (x right, y up, z towards the camera); default: straight up")
+    ap.add_argument("--depth", type=float, default=None, help="with --sphere and --ground: the distance of the sphere's centre")
+    ap.add_argument("--occluders", default=None, help="with --gbuffer and --ground: (K, 4) camera-space spheres (cx, cy, cz, r), K <= 16")
     ap.add_argument("--out", default="inserted.npy")
     return ap
 
 
 def main(argv=None, device=None):
     args = build_parser().parse_args(argv)
-    for p in (args.pano, args.image, args.out):
+    for p in (args.pano, args.image, args.out) + ((args.occluders,) if args.occluders else ()):
         if not p.endswith(".npy"):
             raise SystemExit("%s: the format is .npy only" % p)
+    if args.ground is None and (args.depth is not None or args.occluders is not None):
+        raise SystemExit("--depth and --occluders describe the shadow's occluder: they need --ground HEIGHT")
+    if args.ground is not None:
+        if args.sphere is not None and (args.depth is None or args.occluders is not None):
+            raise SystemExit("--ground with --sphere needs --depth Z (the occluder is the sphere itself, not --occluders)")
+        if args.gbuffer is not None and (args.occluders is None or args.depth is not None):
+            raise SystemExit("--ground with --gbuffer needs --occluders FILE.npy (a G-buffer carries no geometry; --depth goes with --sphere)")
     from . import _runtime
     from .RegressionNetwork.util import TonemapHDR
     _runtime.entry_point_defaults()
@@ -334,6 +452,25 @@ def main(argv=None, device=None):
         exposure = alpha.to(torch.float32) ** args.gamma              # clamp(alpha^gamma I)^(1/gamma) = clamp(alpha I^(1/gamma))
     else:
         exposure = torch.full((1,), float(args.exposure), dtype=torch.float32, device=dev)
+    if args.ground is not None:                                       # the shadow goes onto the HDR image; the exposure stays
+        if args.sphere is not None:
+            try:
+                occ = sphere_occluder(h, w, args.sphere[:2], args.sphere[2], args.depth, args.fov, device=dev)
+            except ValueError as e:
+                raise SystemExit(str(e))
+        else:
+            a = np.asarray(np.load(args.occluders), dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] > MAX_OCCLUDERS:
+                raise SystemExit("--occluders (%s): expected (K, 4) with K <= %d, got %s" % (args.occluders, MAX_OCCLUDERS, a.shape))
+            occ = torch.from_numpy(a[None]).to(dev)
+        ln = math.sqrt(sum(float(v) ** 2 for v in args.ground_normal))
+        if not (ln > 0.0 and math.isfinite(ln)):
+            raise SystemExit("--ground_normal: the normal is zero or not finite")
+        try:                                                          # a unit normal: HEIGHT is then the camera's distance
+            image = ground_shadow(pano, occ, tuple(float(v) / ln for v in args.ground_normal) + (args.ground,), fov_deg=args.fov,
+                                  view_azimuth_deg=args.azimuth, image=image)[1]
+        except ValueError as e:
+            raise SystemExit(str(e))
     background = (image * exposure.view(1, 1, 1, 1)).clamp(0.0, 1.0) ** (1.0 / args.gamma)
     out = insert_object(pano, normal, coverage, background, exposure, kd, ks, km, gamma=args.gamma, fov_deg=args.fov,
                         view_azimuth_deg=args.azimuth, phong_exponent=args.phong)

@@ -311,6 +311,43 @@ int eml_pano_warp_depth_f32(const float* pano, const float* depth, int B, int H,
 int eml_gt_anchor_depth_f64(const float* depth, const int* csr_ptr, const int* csr_pix, int B, int H, int W, int N, double* out,
                             eml_stream_t stream);
 
+/* ---------------------------------------------------------------- object insertion: the shadow on a ground plane
+ * The reference tree has no such code; DESIGN.md section 28 is the definition (differential rendering with a diffuse shadow
+ * catcher), the camera is eml_gbuffer_shade_f32's (RegressionNetwork/util.py:157-174), the grid section 15's.
+ * pano (B,3,H,W) f32, W == 2H; plane: (nx, ny, nz, d) f32 on the device in CAMERA space (x image right, y image up, z towards
+ * the camera), image b reads plane + b * plane_stride (0: one plane for the batch; else >= 4); occluders (B,K,4) f32: spheres
+ * (cx, cy, cz, r) in camera space, 0 <= K <= 16, a sphere whose r is not > 0 (0, negative, NaN) is ignored (padding), one
+ * with r = +inf holds every finite point.  All in f64:
+ *   n = the plane's normal, normalised (d scaled with it), in the panorama's frame; the plane's points q have n.q + d = 0
+ *   E0[b,ch] = sum_t pano[b,ch,t] max(n . omega_t, 0) dOmega_t
+ *   pixel (i, j) with eml_gbuffer_shade_f32's unit ray hits the plane iff n . ray < 0, at p = (-d / (n . ray)) ray
+ *   blocked(p, omega_t): for some sphere k with r_k > 0, oc = c_k - p, s = oc . omega_t:  |oc|^2 < r_k^2 (p inside the
+ *     sphere), or s > 0 and |oc|^2 - s^2 < r_k^2
+ *   D[b,ch,i,j] = sum over the blocked texels of pano[b,ch,t] max(n . omega_t, 0) dOmega_t  (a texel counts once)
+ *   ratio = clamp(1 - D / E0, 0, 1) where the pixel hits the plane and E0[b,ch] > 0, exactly 1 elsewhere; a pixel inside a
+ *   sphere is exactly 0; rounded to f32 once.  shadowed = image * ratio (one f32 product).
+ * A plane with a zero or non-finite normal or with d not > 0 makes every value of that image NaN (the host cannot see a
+ * device plane without a synchronisation; emlight_amd.insert refuses such a plane when it is given as numbers).
+ * ratio (B,3,h,w) and shadowed (B,3,h,w) may each be NULL, not both; image (B,3,h,w) goes with shadowed.  The bits of either
+ * output do not depend on the other being asked for.  Three launches: the per-texel terms and their 256-texel partial sums,
+ * E0, the pixels (8 x 8 per wave).  The order of every sum is fixed (no atomics): run-to-run exact; a pixel adds its blocked
+ * texels rows ascending, columns ascending, each texel once however many spheres block it, so an image's result does not
+ * depend on the batch nor on the order of the spheres, and a padded or hidden sphere changes no bit.  Per wave and sphere only the hull of the 64 pixels' caps (asin(r / |oc|) about oc, as a row range
+ * and a column interval that may wrap the seam; all columns when a cap holds a pole) is walked, less the rows under the
+ * plane's horizon: culling skips only texels whose test is false or whose term is 0.
+ * work: eml_ground_shadow_work_floats(B, H, h, w, K) floats (0 when a size is refused or B == 0), 8-byte aligned: the
+ * 3 B (1 + ceil(2 H^2 / 256) + 2 H^2) doubles of the sums.  Only a library built with -DEML_GROUND_SHADOW_COUNTS (an
+ * experiment build for tools/bench_ground_shadow.py) asks for more and writes, behind them, one uint64 per wave (4 per
+ * 16 x 16 tile, tiles row-major per image): the texel tests that wave executed, 64 lanes per texel walked.
+ * Limits: 0 <= B <= 65535 (B == 0 returns 0), 1 <= H <= 1024, 2 <= h, w <= 16384, 0 < fov_deg < 180 (an orthographic camera's
+ * rays would need origins).  EML_EINVAL, with nothing enqueued: a NULL pano, plane or work; NULL occluders with K > 0; both
+ * outputs NULL; image without shadowed or shadowed without image; W != 2H; K outside 0..16; a plane_stride of 1..3 or < 0;
+ * fov_deg outside (0, 180) or a non-finite azimuth; limits; a misaligned work. */
+size_t eml_ground_shadow_work_floats(int B, int H, int h, int w, int K);
+int eml_ground_shadow_f32(const float* pano, int B, int H, int W, const float* plane, int plane_stride, const float* occluders,
+                          int K, int h, int w, double fov_deg, double view_azimuth_deg, const float* image, float* ratio,
+                          float* shadowed, float* work, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
