@@ -283,6 +283,10 @@ EXT_SIGNATURES = {
     "eml_ground_shadow_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int]),
     "eml_ground_shadow_f32": (_int, [_f32p, _int, _int, _int, _f32p, _int, _f32p, _int, _int, _int, ctypes.c_double,
                                      ctypes.c_double, _f32p, _f32p, _f32p, _f32p, _stream]),
+    # ... and its adjoint: gradients for the panorama and the image
+    "eml_ground_shadow_bwd_work_floats": (ctypes.c_size_t, [_int, _int, _int, _int, _int]),
+    "eml_ground_shadow_bwd_f32": (_int, [_f32p, _int, _int, _int, _f32p, _int, _f32p, _int, _int, _int, ctypes.c_double,
+                                         ctypes.c_double, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _stream]),
 }
 
 _lock = threading.Lock()

@@ -299,25 +299,14 @@ def _plane_arg(plane, B, device):
     return _filled(vals, device), 0
 
 
-def ground_shadow(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, view_azimuth_deg=180.0, size=None, image=None):
-    """The shadow ``occluders (B, K, 4)`` -- spheres ``(cx, cy, cz, r)`` in camera space (x image right, y image up, z towards
-    the camera), ``0 <= K <= 16``, ``r <= 0`` or NaN ignored, ``r = inf`` holds every point -- cast on the ground plane
-    ``n.q + d = 0`` (``plane = (nx, ny, nz, d)`` in camera space, one for the batch or a ``(B, 4)`` device tensor; the four numbers are the equation's coefficients, the
-    normal is normalised here and ``d`` with it, so with a unit normal ``d`` is the camera's distance; ``d > 0``; the default
-    is a floor one unit below a level camera) under the panorama ``pano (B, 3, H, 2H)``, seen by ``shade_gbuffer``'s camera.
-    -> ``ratio (B, 3, h, w)`` in [0, 1]: per pixel that shows the plane and per channel, the cosine-weighted irradiance with
-    the spheres in the way over the irradiance without them; exactly 1 where the pixel misses the plane or the channel's
-    irradiance is 0, exactly 0 where the plane's point is inside a sphere.  ``size=(h, w)`` is required without ``image``;
-    with ``image (B, 3, h, w)`` (the HDR photograph) -> ``(ratio, shadowed)`` with ``shadowed = image * ratio``, what
-    ``composite`` takes as the background once tonemapped.  ``ratio`` does not look at the object's coverage: the composite
-    overwrites those pixels.  A plane given as a device tensor cannot be checked here: a zero normal or ``d <= 0`` makes that
-    image NaN.  ``eml_ground_shadow_f32``; only enqueues work, run-to-run exact, an image's result does not depend on the
-    batch.  The unit of length is arbitrary, shared by plane and spheres."""
+def _shadow_args(pano, occluders, plane, fov_deg, view_azimuth_deg, size, image):
+    """The checked arguments of ``ground_shadow`` (and of its adjoint in ``insert_grad``):
+    -> (pano, occluders, K, plane tensor, plane stride, image or None, h, w, fov, azimuth)."""
     fov, az = _camera(fov_deg, view_azimuth_deg)
     if fov == 0.0:
         raise ValueError("fov_deg must be in (0, 180): the rays of an orthographic camera would need origins, got %r" % (fov_deg,))
     x = _pano_arg(pano)
-    B, _, H, W = x.shape
+    B = x.shape[0]
     occ = _lib.require_gpu_tensor(_forward_only(occluders, "occluders"), "occluders")
     if occ.dim() != 3 or occ.shape[0] != B or occ.shape[2] != 4 or occ.shape[1] > MAX_OCCLUDERS:
         raise ValueError("occluders: expected (%d, K, 4) with K <= %d, got %s" % (B, MAX_OCCLUDERS, tuple(occ.shape)))
@@ -337,6 +326,25 @@ def ground_shadow(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, 
     if h < 2 or w < 2:
         raise ValueError("the image size: expected h, w >= 2, got %s" % ((h, w),))
     pl, stride = _plane_arg(plane, B, x.device)
+    return x, occ, K, pl, stride, img, h, w, fov, az
+
+
+def ground_shadow(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, view_azimuth_deg=180.0, size=None, image=None):
+    """The shadow ``occluders (B, K, 4)`` -- spheres ``(cx, cy, cz, r)`` in camera space (x image right, y image up, z towards
+    the camera), ``0 <= K <= 16``, ``r <= 0`` or NaN ignored, ``r = inf`` holds every point -- cast on the ground plane
+    ``n.q + d = 0`` (``plane = (nx, ny, nz, d)`` in camera space, one for the batch or a ``(B, 4)`` device tensor; the four numbers are the equation's coefficients, the
+    normal is normalised here and ``d`` with it, so with a unit normal ``d`` is the camera's distance; ``d > 0``; the default
+    is a floor one unit below a level camera) under the panorama ``pano (B, 3, H, 2H)``, seen by ``shade_gbuffer``'s camera.
+    -> ``ratio (B, 3, h, w)`` in [0, 1]: per pixel that shows the plane and per channel, the cosine-weighted irradiance with
+    the spheres in the way over the irradiance without them; exactly 1 where the pixel misses the plane or the channel's
+    irradiance is 0, exactly 0 where the plane's point is inside a sphere.  ``size=(h, w)`` is required without ``image``;
+    with ``image (B, 3, h, w)`` (the HDR photograph) -> ``(ratio, shadowed)`` with ``shadowed = image * ratio``, what
+    ``composite`` takes as the background once tonemapped.  ``ratio`` does not look at the object's coverage: the composite
+    overwrites those pixels.  A plane given as a device tensor cannot be checked here: a zero normal or ``d <= 0`` makes that
+    image NaN.  ``eml_ground_shadow_f32``; only enqueues work, run-to-run exact, an image's result does not depend on the
+    batch.  The unit of length is arbitrary, shared by plane and spheres."""
+    x, occ, K, pl, stride, img, h, w, fov, az = _shadow_args(pano, occluders, plane, fov_deg, view_azimuth_deg, size, image)
+    B, _, H, W = x.shape
     ratio = torch.empty(B, 3, h, w, dtype=torch.float32, device=x.device)
     shadowed = torch.empty_like(ratio) if img is not None else None
     if B > 0:

@@ -9,10 +9,17 @@
   sample's bits do not depend on its batch or on what else was asked for.  ``dpano`` of ``shade_gbuffer`` is autograd's sum of
   the mirror scatter and the prefilter adjoints of the two map gradients.
 * ``InsertionLoss``: "the inserted object looks right" for an arbitrary G-buffer, as a training term.
+* ``ground_shadow`` (``csrc/ground_shadow_bwd.hip``; ``tests/shadow_grad_oracle.py``): gradients for
+  ``pano`` and ``image``.  The ratio is ``1 - D / E0``, two linear functionals of the panorama, so the gradient is closed
+  form; its hot path, the scatter over the binary visibility, reruns the forward's walk and adds in 64-bit fixed point.  The
+  gradient is that of the unclamped ratio: a non-negative panorama never reaches the clamp to [0, 1]; where negative texels
+  make it bind, it is passed straight through.  ``ShadowLoss``: "the shadow falls right", as a training term.
 
-Numbers and RGB triples get no gradient.  ``normal``, ``coverage``, ``background`` and ``exposure`` have no gradient defined:
-one that requires grad is refused by name.  When nothing requires grad, or grad mode is off, every call here makes exactly
-the launches of ``emlight_amd.insert`` and returns the same bits.  Everything only enqueues work.
+Numbers and RGB triples get no gradient.  ``normal``, ``coverage``, ``background`` and ``exposure`` have no gradient defined,
+nor have the shadow's ``plane`` and ``occluders`` (visibility is binary: its derivative is zero almost everywhere and a
+distribution on the silhouettes): one that requires grad is refused by name.  When nothing requires grad, or grad mode is
+off, every call here makes exactly the launches of ``emlight_amd.insert`` and returns the same bits.  Everything only
+enqueues work.
 """
 import ctypes
 
@@ -118,6 +125,57 @@ def shade_gbuffer_bwd_raw(grad_out, pano=None, maps=(None, None), normal=None, c
             _lib.ptr(out.get("kd")), _lib.ptr(out.get("ks")), _lib.ptr(out.get("km")), _lib.ptr(out.get("e_diffuse")),
             _lib.ptr(out.get("e_phong")), _lib.ptr(out.get("pano")), _lib.ptr(out.get("shaded")), _lib.ptr(work),
             _lib.current_stream()), "eml_gbuffer_shade_bwd_f32")
+    return out
+
+
+def _no_shadow_gradient(t, name):
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("%s requires grad: no gradient is defined for %s (visibility is binary; DESIGN section 29 "
+                         "differentiates pano and image); pass %s.detach()" % (name, name, name))
+    return t
+
+
+def ground_shadow_bwd_raw(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, view_azimuth_deg=180.0, size=None,
+                          image=None, g_ratio=None, g_shadowed=None, want=("pano",)):
+    """``eml_ground_shadow_bwd_f32`` without autograd.  The scene as ``ground_shadow`` takes it; ``g_ratio`` and ``g_shadowed``
+    ``(B, 3, h, w)`` are the gradients of its two outputs, either may be None, ``g_shadowed`` needs ``image``.  ``want``: some of
+    ``"pano"`` and ``"image"`` (which needs ``g_shadowed``); what is not named is passed as NULL and not computed.
+    -> dict name -> tensor: ``pano (B, 3, H, 2H)``, ``image (B, 3, h, w)``."""
+    want = tuple(want)
+    if not want or any(n not in ("pano", "image") for n in want):
+        raise ValueError("want: expected some of ('pano', 'image'), got %r" % (want,))
+    if g_ratio is None and g_shadowed is None:
+        raise ValueError("g_ratio and g_shadowed: at least one gradient is required")
+    if g_shadowed is not None and image is None:
+        raise ValueError("g_shadowed needs image (shadowed = image * ratio)")
+    if "image" in want and g_shadowed is None:
+        raise ValueError("want 'image' needs g_shadowed (dimage = g_shadowed * ratio)")
+    if size is None and image is None:
+        size = tuple((g_ratio if g_ratio is not None else g_shadowed).shape[2:])
+    x, occ, K, pl, stride, img, h, w, fov, az = _insert._shadow_args(pano, occluders, plane, fov_deg, view_azimuth_deg, size,
+                                                                     image)
+    B, _, H, W = x.shape
+    grads = []
+    for t, nm in ((g_ratio, "g_ratio"), (g_shadowed, "g_shadowed")):
+        if t is not None:
+            t = _lib.require_gpu_tensor(t, nm)
+            if tuple(t.shape) != (B, 3, h, w):
+                raise ValueError("%s: expected %s, got %s" % (nm, (B, 3, h, w), tuple(t.shape)))
+        grads.append(t)
+    out = {}
+    if "pano" in want:
+        out["pano"] = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    if "image" in want:
+        out["image"] = torch.empty(B, 3, h, w, dtype=torch.float32, device=x.device)
+    if B > 0:
+        L = _lib.lib()
+        work = torch.empty(max(1, (L.eml_ground_shadow_bwd_work_floats(B, H, h, w, K) + 1) // 2), dtype=torch.float64,
+                           device=x.device)                          # doubles: 8-byte aligned
+        _lib.check(L.eml_ground_shadow_bwd_f32(_lib.ptr(x), B, H, W, _lib.ptr(pl), stride, _lib.ptr(occ) if K > 0 else None, K,
+                                               h, w, fov, az, _lib.ptr(img) if grads[1] is not None else None,
+                                               _lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(out.get("pano")),
+                                               _lib.ptr(out.get("image")), _lib.ptr(work), _lib.current_stream()),
+                   "eml_ground_shadow_bwd_f32")
     return out
 
 
@@ -254,6 +312,54 @@ def insert_object(pano, normal, coverage, background, exposure, kd=None, ks=None
                   glossy_height, maps, background, exposure, gamma)
 
 
+class _Shadow(torch.autograd.Function):
+    """One forward call; the adjoint reruns the forward's walk from the forward's inputs, nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, pano, image, occluders, plane, fov, az, size):
+        out = _insert.ground_shadow(pano, occluders, plane, fov_deg=fov, view_azimuth_deg=az, size=size, image=image)
+        tensors = [pano, occluders] + [t for t in (image, plane) if isinstance(t, torch.Tensor)]
+        ctx.save_for_backward(*tensors)
+        ctx.scene = (image is not None, plane if not isinstance(plane, torch.Tensor) else None, fov, az, tuple(out[0].shape[2:])
+                     if image is not None else tuple(out.shape[2:]))
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ratio, g_shadowed=None):
+        saved = list(ctx.saved_tensors)
+        has_image, plane, fov, az, size = ctx.scene
+        pano, occluders = saved[0].detach(), saved[1].detach()
+        image = saved[2].detach() if has_image else None
+        if plane is None:
+            plane = saved[-1].detach()
+        want = tuple(nm for nm, need in zip(("pano", "image"), ctx.needs_input_grad)
+                     if need and (nm == "pano" or g_shadowed is not None))
+        if not want or (g_ratio is None and g_shadowed is None):
+            return (None,) * 7
+        got = ground_shadow_bwd_raw(pano, occluders, plane, fov_deg=fov, view_azimuth_deg=az, size=size,
+                                    image=image if g_shadowed is not None else None, g_ratio=g_ratio, g_shadowed=g_shadowed,
+                                    want=want)
+        return (got.get("pano"), got.get("image")) + (None,) * 5
+
+
+def ground_shadow(pano, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, fov_deg=60.0, view_azimuth_deg=180.0, size=None, image=None):
+    """``emlight_amd.insert.ground_shadow``, differentiable in ``pano`` and in ``image`` (``eml_ground_shadow_bwd_f32``): the
+    same arguments, the same returns, the same bits.  ``dpano = wgt / E0 (S - G)`` with ``S = sum_p g (1 - v)`` and
+    ``G[t] = sum_p g blocked(p, t)`` over the pixels that hit the plane outside every sphere, ``g = g_ratio + g_shadowed image``;
+    ``dimage = g_shadowed ratio``.  The gradient is that of the unclamped ratio: a non-negative panorama never reaches the
+    clamp, and where negative texels make it bind it is passed straight through.  ``plane`` and ``occluders`` have no
+    gradient (visibility is binary): one that requires grad is refused by name."""
+    _no_shadow_gradient(plane, "plane"), _no_shadow_gradient(occluders, "occluders")
+    if not _needs(pano, image):
+        return _insert.ground_shadow(pano, occluders, plane, fov_deg=fov_deg, view_azimuth_deg=view_azimuth_deg, size=size,
+                                     image=image)
+    with torch.no_grad():                                             # every refusal of the forward, before anything is recorded
+        _, _, _, _, _, _, h, w, fov, az = _insert._shadow_args(pano, occluders, plane, fov_deg, view_azimuth_deg, size, image)
+    return _Shadow.apply(pano, image, occluders, plane, fov, az, (h, w))
+
+
 # ------------------------------------------------------------------------------------------------ a training term
 def _shade_pair(loss, pred, true):
     """The shaded images of ``pred`` and ``true`` from one prefilter call per lobe and one shading call over ``2B`` images:
@@ -347,3 +453,85 @@ class InsertionLoss(torch.nn.Module):
         d = a - b
         return ((self.coverage * d * d).sum((1, 2, 3)) / self.denominator).mean()
 
+
+class _ShadowPair(torch.autograd.Function):
+    """The shadow ratios of ``pred`` and ``true`` from one forward over ``2B`` images, for a ``pred`` that requires grad.
+    ``true``'s images are not differentiable and the adjoint runs over ``pred``'s images only."""
+
+    @staticmethod
+    def forward(ctx, pred, true, loss):
+        B = pred.shape[0]
+        out = loss.ratios(pred, true)
+        ctx.save_for_backward(pred)
+        ctx.loss = loss
+        a, b = out[:B], out[B:]
+        ctx.mark_non_differentiable(b)
+        return a, b
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        loss = ctx.loss
+        got = ground_shadow_bwd_raw(ctx.saved_tensors[0].detach(), loss.occluders, loss.plane, fov_deg=loss.fov_deg,
+                                    view_azimuth_deg=loss.view_azimuth_deg, size=loss.size, g_ratio=g.contiguous())
+        return got["pano"], None, None
+
+
+class ShadowLoss(torch.nn.Module):
+    """"The shadow falls right", as a training term: the mean over images of ``sum weight (a - b)^2 / (3 sum weight)`` with
+    ``a``, ``b`` the shadow ratios (``ground_shadow``: ``occluders (B, K, 4)``, ``plane`` four numbers or a ``(B, 4)`` tensor,
+    ``size=(h, w)``) under the predicted and the true panorama.  ``weight (B, 1, h, w)`` defaults to all ones; pass
+    ``1 - coverage`` to ignore the pixels the object hides.  Both panoramas go through ONE forward over ``2B`` images; the
+    truth gets no gradient and the adjoint runs over the prediction's images only.  A misplaced or over-blurred light gives a
+    wrong or missing shadow where the shaded object still looks plausible: this term sees it.  Only enqueues work."""
+
+    def __init__(self, occluders, plane=(0.0, 1.0, 0.0, 1.0), *, size, fov_deg=60.0, view_azimuth_deg=180.0, weight=None):
+        super().__init__()
+        _no_shadow_gradient(occluders, "occluders"), _no_shadow_gradient(plane, "plane"), _no_gradient(weight, "weight")
+        self.fov_deg, self.view_azimuth_deg = _insert._camera(fov_deg, view_azimuth_deg)
+        self.size = tuple(int(v) for v in size)
+        with torch.no_grad():
+            occ = _lib.require_gpu_tensor(occluders, "occluders")
+            if occ.dim() != 3 or occ.shape[0] < 1 or occ.shape[2] != 4 or occ.shape[1] > _insert.MAX_OCCLUDERS:
+                raise ValueError("occluders: expected (B, K, 4) with B >= 1 and K <= %d, got %s"
+                                 % (_insert.MAX_OCCLUDERS, tuple(occ.shape)))
+            B, (h, w) = occ.shape[0], self.size
+            if h < 2 or w < 2:
+                raise ValueError("size: expected h, w >= 2, got %s" % (self.size,))
+            if weight is None:
+                wt = torch.ones(B, 1, h, w, dtype=torch.float32, device=occ.device)
+            else:
+                wt = _lib.require_gpu_tensor(weight, "weight")
+                if tuple(wt.shape) != (B, 1, h, w):
+                    raise ValueError("weight: expected %s, got %s" % ((B, 1, h, w), tuple(wt.shape)))
+            self.register_buffer("occluders", occ.detach(), persistent=False)
+            self.register_buffer("occluders2", torch.cat([occ, occ], 0).detach(), persistent=False)
+            self.register_buffer("weight", wt.detach(), persistent=False)
+            self.register_buffer("denominator", 3.0 * wt.sum((1, 2, 3)), persistent=False)
+            if isinstance(plane, torch.Tensor):
+                pl, _ = _insert._plane_arg(plane, B, occ.device)
+                self.register_buffer("plane", pl.detach(), persistent=False)
+                self.register_buffer("plane2", torch.cat([pl, pl], 0).detach(), persistent=False)
+            else:
+                _insert._plane_arg(plane, B, occ.device)              # its refusals, now
+                self.plane = self.plane2 = tuple(float(v) for v in plane)
+
+    def ratios(self, pred, true):
+        """ratio (2B, 3, h, w): the prediction's images, then the truth's, from one forward call."""
+        return _insert.ground_shadow(torch.cat([pred, true], 0), self.occluders2, self.plane2, fov_deg=self.fov_deg,
+                                     view_azimuth_deg=self.view_azimuth_deg, size=self.size)
+
+    def forward(self, pred, true):
+        p = _insert._pano_arg(pred.detach() if isinstance(pred, torch.Tensor) else pred)
+        t = _insert._pano_arg(true.detach() if isinstance(true, torch.Tensor) else true)
+        B = self.occluders.shape[0]
+        if p.shape != t.shape or p.shape[0] != B:
+            raise ValueError("pred %s and true %s: expected two equal shapes (%d, 3, H, 2H)" % (tuple(p.shape), tuple(t.shape), B))
+        if _needs(pred):
+            a, b = _ShadowPair.apply(pred, t, self)
+        else:
+            with torch.no_grad():
+                out = self.ratios(p, t)
+            a, b = out[:B], out[B:]
+        d = a - b
+        return ((self.weight * d * d).sum((1, 2, 3)) / self.denominator).mean()

@@ -348,6 +348,30 @@ int eml_ground_shadow_f32(const float* pano, int B, int H, int W, const float* p
                           int K, int h, int w, double fov_deg, double view_azimuth_deg, const float* image, float* ratio,
                           float* shadowed, float* work, eml_stream_t stream);
 
+/* The adjoint of eml_ground_shadow_f32 (tests/shadow_grad_oracle.py): gradients for the panorama and
+ * for the image.  With wgt[t] = max(n . omega_t, 0) dOmega_t, v = 1 - D / E0 and g = g_ratio + g_shadowed * image (in f64;
+ * either gradient may be NULL, not both), over the active pixels (the pixel hits the plane, is not inside a sphere, E0 > 0):
+ *   S[b,ch] = sum_p g (1 - v)      G[b,ch,t] = sum_p g blocked(p, t)
+ *   dpano[b,ch,t]  = wgt[t] / E0[b,ch] (S - G)     (exactly 0 where wgt = 0 and for the whole of a channel with E0 <= 0)
+ *   dimage[b,ch,p] = g_shadowed * ratio            (one f32 product of the forward's f32 ratio)
+ * The gradient is that of the unclamped v: for a non-negative panorama 0 <= v <= 1 always holds; where negative texels make
+ * the clamp bind, it is passed straight through.  Pixels inside a sphere, pixels off the plane and black channels add exactly
+ * nothing.  plane and occluders get no gradient (visibility is binary).  Nothing is kept from the forward but its inputs: the
+ * walk is the forward's own (csrc/ground_shadow_walk.h), every lane ends with the forward's D bit for bit.  G is a scatter,
+ * added in 64-bit fixed point (units of 2^(e-61) with 2^e > sum_p |g| per image and channel) with integer atomics; every
+ * other sum has a fixed order and there are no float atomics: run-to-run exact, an image's gradient does not depend on the
+ * batch nor on the order of the spheres, a padded or hidden sphere changes no bit, and the bits of either output do not
+ * depend on the other being asked for.
+ * dpano (B,3,H,W) and dimage (B,3,h,w) may each be NULL, not both; g_shadowed needs image, dimage needs g_shadowed.
+ * work: eml_ground_shadow_bwd_work_floats(B, H, h, w, K) floats (0 when a size is refused or B == 0), 8-byte aligned.
+ * Limits and EML_EINVAL as eml_ground_shadow_f32, and: both gradients NULL; both outputs NULL; g_shadowed without image;
+ * dimage without g_shadowed.  B == 0 returns 0. */
+size_t eml_ground_shadow_bwd_work_floats(int B, int H, int h, int w, int K);
+int eml_ground_shadow_bwd_f32(const float* pano, int B, int H, int W, const float* plane, int plane_stride,
+                              const float* occluders, int K, int h, int w, double fov_deg, double view_azimuth_deg,
+                              const float* image, const float* g_ratio, const float* g_shadowed, float* dpano, float* dimage,
+                              float* work, eml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
